@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py — SimRank iterations/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pl32768] [--mode auto]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload pl32768] [--mode auto] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: the headline and what the HIP events of
+the timed steps give (``roofline``).  Everything else — the short-circuit convergence test, convergence to eps,
+the other BASELINE configurations, fit() wall clocks, diagnostic launches, the CPU baseline, the link probe of
+several ranks and the complete record (``--full-json``) — runs with ``--full`` only.  ``--dump-outputs DIR``
+writes what the timed loop computed in its last step (see ``dump_outputs``).
 
 A "step" is one loop body of the reference's ``fit`` (SimRank.py:138-140): both legs of
 S <- C.W.S.W^T with the fused diagonal/convergence epilogue, plus the read-back of the
@@ -210,6 +216,21 @@ def write_full(out, path):
     except OSError:
         pass
 
+DUMP_S_BYTES = 32 << 20       # --dump-outputs: bytes of the sampled rows of S (float32)
+
+
+def dump_outputs(path, n, rows_of, changed):
+    """``--dump-outputs DIR``: what a caller of the timed loop receives after its last step, as .npy files —
+    ``S_rows``: float32 [k, n], rows of S in the caller's node order (all rows when they fit in DUMP_S_BYTES, else
+    k of them drawn with np.random.default_rng(0) and sorted: the same rows in every run of the same workload);
+    ``changed``: float64 [1], the count of moved elements that step returned.  ``rows_of(ids)`` reads the rows."""
+    k = max(1, min(n, DUMP_S_BYTES // (4 * n)))
+    ids = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "S_rows.npy"), np.ascontiguousarray(rows_of(ids), dtype=np.float32))
+    np.save(os.path.join(path, "changed.npy"), np.array([changed], dtype=np.float64))
+
+
 def cpu_share():
     """CPUs this process may actually use: the affinity mask, cut by the cgroup's quota (the GPU boxes show 256 hardware
     threads and grant 16 CPUs of time: cpu.max = "1600000 100000")."""
@@ -389,6 +410,8 @@ def c_loop_section(args, ops, world, dist, torch, synth, ingest, csr, coef, gpu,
 
     spec = (csr.rowscale if not args.pp else ingest.spread(csr) * csr.rowscale)
     for name, kw, grade in variants:
+        if not grade and not args.full:
+            continue                                 # (reduced precision: not a candidate for the headline)
         rec = time_variant(csr, spec, args.pp, kw, args.steps, max(1, args.warmup))
         rec["parity_grade"] = grade
         out["variants"][name] = rec
@@ -439,8 +462,9 @@ def c_loop_section(args, ops, world, dist, torch, synth, ingest, csr, coef, gpu,
         except Exception as e:
             out["config3"] = {"error": f"{type(e).__name__}: {e}"}
     # LAST (a probe that hangs must not cost the measurements above: the watchdog prints what is there): what the links move
-    barrier()
-    out["link_probe"] = link_probe(world, dist, torch, rank)
+    if args.full:
+        barrier()
+        out["link_probe"] = link_probe(world, dist, torch, rank)
     return out
 
 
@@ -541,7 +565,8 @@ def c_loop_only(err):
     if not err:
         out.pop("python_world_error", None)
     if rank == 0:
-        write_full(out, getattr(args, "full_json", None))
+        if args.full:
+            write_full(out, getattr(args, "full_json", None))
         st["emit"](compact_line(out))
     try:
         st["dist"].destroy_process_group()
@@ -558,6 +583,13 @@ def main():
     ap.add_argument("--workload", default="pl32768d32")
     ap.add_argument("--mode", default="auto")
     ap.add_argument("--panel", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else (short-circuit convergence test, "
+                         "convergence to eps, the other BASELINE configurations, fit() wall clocks, diagnostic launches, "
+                         "CPU baseline, link probe) and write --full-json; --no-extras, --no-cpu-baseline and --exact-only "
+                         "trim that run.  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed loop computed in its last step to DIR/<name>.npy (one process only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--full-json", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
@@ -591,6 +623,11 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="use the torch.distributed world even with one rank (exercises RCCL)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.c_loop_only):
+        ap.error("--dump-outputs: one process only (the sharded C loop hands its result back on rank 0 alone)")
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_extras = args.no_cpu_baseline = args.exact_only = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))           # before anything touches torch or HIP
@@ -702,12 +739,14 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            hplan.step(0.0, exact_count=True)
+            changed = hplan.step(0.0, exact_count=True)
         barrier()
         elapsed = time.perf_counter() - t0
         l1p, l2p, n_stamped = hplan.leg_times()
         hplan.set_timing(0)
         legs = {"leg1.0": (l1p, n_stamped), "leg2.0": (l2p, n_stamped)}
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, n, hplan.rows, changed)
         if not args.exact_only:
             hplan.step(0.0, exact_count=False)
             barrier()
@@ -723,7 +762,7 @@ def main():
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            solver.step(0.0)
+            changed = solver.step(0.0)
         barrier()
         elapsed = time.perf_counter() - t0
         if use_dist:
@@ -732,6 +771,8 @@ def main():
             elapsed = float(t.item())
         legs = solver.leg_times()                 # mean ms per launch, measured by HIP events
         solver.events = None
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, n, lambda ids: solver.result(0)[ids], changed)
     side = solver.sides[0][rank if use_dist else 0]
     side_stages = side.n_stages
     out = {
@@ -879,7 +920,7 @@ def main():
                     out["roofline_mfma"]["phase_alone"] = {"error": f"{type(e).__name__}: {e}"}
                 finally:
                     os.environ.pop("SIMRANK_ENABLE_PROBES", None)
-        elif dk and side.Lk:
+        elif dk and side.Lk and args.full:
             S_in = solver.cur[0][rank if use_dist else 0]
             for _ in range(2):
                 ops.dense_part(side.graph, S_in, side.Lk)
@@ -944,20 +985,21 @@ def main():
                              "Tt read, all of S' written, half of the previous iterate read), not of the full form")
         # what the runtime's own device-to-device copy of S moves per second on this GPU (read +
         # write): the practical ceiling next to the 8 TB/s spec figure used for `frac`
-        try:
-            src, dst = solver.cur[0][rank if use_dist else 0], solver.nxt[0][rank if use_dist else 0]
-            ops.copy(dst, src)
-            e0, e1 = ops.event(), ops.event()
-            ops.record(e0)
-            for _ in range(3):
+        if args.full:
+            try:
+                src, dst = solver.cur[0][rank if use_dist else 0], solver.nxt[0][rank if use_dist else 0]
                 ops.copy(dst, src)
-            ops.record(e1)
-            copy_gbs = 2 * src.nbytes / (ops.elapsed_ms(e0, e1) / 3 * 1e-3) / 1e9
-            for r in rl:
-                r["box_memcpy_GBps"] = copy_gbs
-                r["frac_of_box_memcpy"] = r["achieved"] / copy_gbs
-        except Exception:
-            pass
+                e0, e1 = ops.event(), ops.event()
+                ops.record(e0)
+                for _ in range(3):
+                    ops.copy(dst, src)
+                ops.record(e1)
+                copy_gbs = 2 * src.nbytes / (ops.elapsed_ms(e0, e1) / 3 * 1e-3) / 1e9
+                for r in rl:
+                    r["box_memcpy_GBps"] = copy_gbs
+                    r["frac_of_box_memcpy"] = r["achieved"] / copy_gbs
+            except Exception:
+                pass
         rl.sort(key=lambda r: -r["ms"])
         out["roofline"], out["roofline_other"] = rl[0], rl[1]
     else:
@@ -1532,7 +1574,8 @@ def main():
             out["cpu_baseline"] = cpu_baseline(csr, S_host, coef)
             out["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
     if rank == 0:
-        write_full(out, args.full_json)
+        if args.full:
+            write_full(out, args.full_json)
         emit(compact_line(out))
     STATE["emitted"] = True
     if use_dist:

@@ -544,7 +544,7 @@ def test_rccl_world_of_one_rank():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
            "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "er8192", "--force-dist",
-           "--stages", "3", "--no-cpu-baseline"]
+           "--stages", "3", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
