@@ -40,7 +40,7 @@
 extern "C" {
 #endif
 
-#define SIMRANK_ABI_VERSION 7
+#define SIMRANK_ABI_VERSION 8
 #define SIMRANK_CHANGED_SLOTS 1024
 
 #if defined(__GNUC__)
@@ -399,6 +399,10 @@ SIMRANK_API int simrank_graph_dense_stats(const simrank_graph* g, int64_t* n_til
  *      16-column matrix-core steps per panel, entries on the matrix cores, entries gathered. */
 SIMRANK_API int simrank_graph_fused_stats(const simrank_graph* g, int64_t* n_steps,
                                           int64_t* nnz_covered, int64_t* nnz_remainder);
+/* What a graph chose when it was built, by key: "fused_ids16" 1 | 0 the one-launch plan streams 16 | 32-bit ids (-1: the
+ * graph has no such plan), "gather_ids16" 1 | 0 the gather kernel streams 16 | 32-bit ids.  SIMRANK_ERR_INVALID (with
+ * the message) for a NULL handle or an unknown key.  (ABI 8) */
+SIMRANK_API int simrank_graph_get(const simrank_graph* g, const char* key, int64_t* value);
 /* The matrix-core part of simrank_spmm alone, into the graph's partial-sum buffer (measurement
  * harness: its HIP-event time and 2 * 3 * 128 * dense_cols * n_cols_x bf16 flop give the MFMA
  * rate).  X needs 8-byte alignment and an even ldx.  Fails when the graph has no dense sets. */
@@ -473,6 +477,10 @@ SIMRANK_API int simrank_plan_rows_f32(simrank_plan* p, const int32_t* rows, int3
 SIMRANK_API int simrank_plan_set_timing(simrank_plan* p, int32_t updates);
 SIMRANK_API int simrank_plan_leg_times(simrank_plan* p, double* leg1_ms, double* leg2_ms, int32_t* updates);
 SIMRANK_API int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* updates, const simrank_graph** graph);
+/* what the plan chose when it was created, by key: "restrict_support" 1 | 0 leg 2 is restricted to supp(E) (tuning
+ * "restrict_support").  SIMRANK_ERR_INVALID for a NULL handle or an unknown key.  (ABI 8; likewise simrank_biplan_get
+ * per group 1 | 2 and simrank_shardplan_get, which also serves the sides of a sharded bipartite plan) */
+SIMRANK_API int simrank_plan_get(const simrank_plan* p, const char* key, int64_t* value);
 SIMRANK_API int simrank_plan_destroy(simrank_plan* p);
 
 /* ---- BIPARTITE PLAN: the loop of BipartiteSimRank.fit / BipartiteSimRankPP.fit / BipartitleAprioriSimRank.fit
@@ -520,6 +528,7 @@ SIMRANK_API int simrank_biplan_topk(simrank_biplan* p, int32_t group, int32_t k,
 SIMRANK_API int simrank_biplan_rows_f32(simrank_biplan* p, int32_t group, const int32_t* rows, int32_t n_rows, float* dst,
                                         int64_t ld);
 SIMRANK_API int simrank_biplan_evidence_u8(simrank_biplan* p, int32_t group, uint8_t* dst, int64_t ld);
+SIMRANK_API int simrank_biplan_get(const simrank_biplan* p, int32_t group, const char* key, int64_t* value);
 SIMRANK_API int simrank_biplan_trim(simrank_biplan* p);
 SIMRANK_API int simrank_biplan_destroy(simrank_biplan* p);
 
@@ -615,6 +624,7 @@ SIMRANK_API int simrank_shardplan_set_timing(simrank_shardplan* p, int32_t updat
 SIMRANK_API int simrank_shardplan_timings(simrank_shardplan* p, double* ms, int32_t n_ms, int32_t* updates);
 SIMRANK_API int simrank_shardplan_info(const simrank_shardplan* p, int64_t* n, int64_t* col_lo, int64_t* col_hi,
                                        int32_t* half_form, int32_t* stages, int32_t* updates);
+SIMRANK_API int simrank_shardplan_get(const simrank_shardplan* p, const char* key, int64_t* value);
 SIMRANK_API int simrank_shardplan_destroy(simrank_shardplan* p);
 
 /* ---- SHARDED BIPARTITE PLAN: the loops of BipartiteSimRank.fit / BipartiteSimRankPP.fit / BipartitleAprioriSimRank.fit
@@ -675,7 +685,11 @@ SIMRANK_API int simrank_shardbiplan_destroy(simrank_shardbiplan* bp);
  *      "fuse_store" cache policy of the tile stores (0 plain, 1 nt, 2 sc1, 3 sc0 sc1); "fuse_meta_nt"
  *      "dense_terms" operand terms of the block-dense part: 3 = bf16 hi+mid+lo (exact f32
  *                 products, default), 1 = one fp16 term (reduced precision, BASELINE config 5)
- *      "ids16"    0/1  stream the neighbour ids as 16-bit values (graphs with <= 65536 columns)
+ *      "ids16"    0/1  stream the neighbour ids as 16-bit values (graphs with <= 65536 columns; the one-launch
+ *                 plan: <= 65535); 0 = 32-bit ids in the gather kernel and the one-launch plan at any size
+ *      "restrict_support" SimRank++ leg 2 restricted to supp(E) (lane groups whose 32 evidence counts are all zero
+ *                 skip their gathers), decided when a plan is created: 1 always (when evidence is given), 0 never,
+ *                 -1 (default) when fewer than half of the 32-column evidence segments are live
  *      "dense_sym" dense part in the upper-triangle form of leg 2: 1 always, 0 never, -1 when
  *                 the dense sets hold at least half of the entries
  *      "sym_desc" 0/1  upper-triangle leg 2: an XCD takes its panels in descending order (default 1)

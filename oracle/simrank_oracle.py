@@ -134,8 +134,10 @@ def bipartite_graph(data: pd.DataFrame, weighted=False, node_group1_column="user
 # --------------------------------------------------------------------------------------
 def evidence(G: np.ndarray) -> np.ndarray:
     """E = 1 - 0.5**(number of common in-neighbours).  SimRank.py:315-316."""
-    pat = (G > 0).astype(np.int64)
-    common = pat @ pat.T
+    pat = (G > 0).astype(np.float64)
+    # (the product in float64 through BLAS: every count is an integer below 2^53, so exact — NumPy's integer
+    # matmul has no BLAS and takes a minute at n = 4096)
+    common = np.rint(pat @ pat.T).astype(np.int64)
     return 1 - 0.5 ** common
 
 

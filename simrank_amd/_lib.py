@@ -39,7 +39,7 @@ class Epilogue(C.Structure):
     ]
 
 
-ABI_VERSION = 7          # SIMRANK_ABI_VERSION of include/simrank_hip.h
+ABI_VERSION = 8          # SIMRANK_ABI_VERSION of include/simrank_hip.h
 # the console hooks of the C-level loops (simrank_progress_fn)
 PROGRESS_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_int32, C.c_int32)
 
@@ -106,6 +106,7 @@ PROTOTYPES = {
     "simrank_biplan_topk": [_vp, _i32, _i32, _i32, _vp, _vp],
     "simrank_biplan_rows_f32": [_vp, _i32, _vp, _i32, _vp, _i64],
     "simrank_biplan_evidence_u8": [_vp, _i32, _vp, _i64],
+    "simrank_biplan_get": [_vp, _i32, C.c_char_p, C.POINTER(_i64)],
     "simrank_biplan_trim": [_vp],
     "simrank_biplan_create": [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "simrank_biplan_reset": [_vp],
@@ -129,6 +130,7 @@ PROTOTYPES = {
     "simrank_graph_dense_stats": [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
     "simrank_graph_set_dense_terms": [_vp, C.c_int32],
     "simrank_graph_fused_stats": [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)],
+    "simrank_graph_get": [_vp, C.c_char_p, C.POINTER(_i64)],
     "simrank_dense_part": [_vp, _vp, _i64, _i64, _vp],
     "simrank_plan_create": [_i64, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)],
     "simrank_plan_reset": [_vp],
@@ -137,6 +139,7 @@ PROTOTYPES = {
     "simrank_plan_result": [_vp, _vp, _i64],
     "simrank_plan_result_f64": [_vp, _vp, _i64],
     "simrank_plan_info": [_vp, C.POINTER(_i64), C.POINTER(C.c_int32), C.POINTER(_vp)],
+    "simrank_plan_get": [_vp, C.c_char_p, C.POINTER(_i64)],
     "simrank_plan_destroy": [_vp],
     "simrank_comm_unique_id": [_vp],
     "simrank_comm_create": [_vp, C.c_int32, C.c_int32, C.POINTER(_vp)],
@@ -154,6 +157,7 @@ PROTOTYPES = {
     "simrank_shardplan_topk": [C.POINTER(_vp), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp],
     "simrank_shardplan_info": [_vp, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32),
                                C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "simrank_shardplan_get": [_vp, C.c_char_p, C.POINTER(_i64)],
     "simrank_shardplan_destroy": [_vp],
     "simrank_shardplan_set_timing": [_vp, C.c_int32],
     "simrank_shardplan_timings": [_vp, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_int32)],

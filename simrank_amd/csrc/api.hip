@@ -979,6 +979,9 @@ int simrank_set_tuning(const char* key, int64_t value) {
     } else if (!strcmp(key, "dense_cols")) {
         SR_REQUIRE(value >= 1 && value <= (1 << 20), "dense_cols must be >= 1");
         t.dense_cols = value;
+    } else if (!strcmp(key, "restrict_support")) {
+        SR_REQUIRE(value >= -1 && value <= 1, "restrict_support must be -1 (automatic), 0 or 1");
+        t.restrict_support = value;
     } else {
         SR_REQUIRE(false, "unknown tuning key '%s'", key);
     }
@@ -1023,7 +1026,16 @@ int simrank_get_tuning(const char* key, int64_t* value) {
     else if (!strcmp(key, "probe_flags")) *value = t.probe_flags;
     else if (!strcmp(key, "dense_terms")) *value = t.dense_terms;
     else if (!strcmp(key, "probe_mask")) *value = t.probe_mask;
+    else if (!strcmp(key, "restrict_support")) *value = t.restrict_support;
     else SR_REQUIRE(false, "unknown tuning key '%s'", key);
+    return SIMRANK_OK;
+}
+
+int simrank_graph_get(const simrank_graph* g, const char* key, int64_t* value) {
+    SR_REQUIRE(g && key && value, "NULL argument");
+    if (!strcmp(key, "fused_ids16")) *value = g->fused ? g->fused->ids16 : -1;
+    else if (!strcmp(key, "gather_ids16")) *value = (g->col16 && g->tun.ids16) ? 1 : 0;
+    else SR_REQUIRE(false, "unknown graph key '%s'", key);
     return SIMRANK_OK;
 }
 

@@ -301,7 +301,7 @@ int simrank_biplan_create(int64_t n1, int64_t n2, int64_t nnz, const int32_t* ro
             int64_t live = 0, total = 1;
             rc = simrank_evidence_live_segments(a.ev, 32, a.rows_pad, a.n, a.n, &live, &total, p->stream);
             if (rc) return fail(rc);
-            a.restrict_support = 2 * live < total ? 1 : 0;
+            a.restrict_support = restrict_choice(a.g->tun, live, total);
         }
         if (priors[w]) {
             float* tmp = nullptr;
@@ -495,6 +495,15 @@ int simrank_biplan_evidence_u8(simrank_biplan* p, int32_t group, uint8_t* dst, i
         return SIMRANK_ERR_HIP;
     }
     return rc;
+}
+
+int simrank_biplan_get(const simrank_biplan* p, int32_t group, const char* key, int64_t* value) {
+    SR_REQUIRE(p && key && value, "NULL argument");
+    SR_REQUIRE(group == 1 || group == 2, "group must be 1 or 2");
+    const side_t& a = p->s[group - 1];
+    if (!strcmp(key, "restrict_support")) *value = a.restrict_support;
+    else SR_REQUIRE(false, "unknown plan key '%s'", key);
+    return SIMRANK_OK;
 }
 
 int simrank_biplan_trim(simrank_biplan* p) {

@@ -55,7 +55,8 @@ struct Tuning {
     int64_t addr32 = 1;      // lean kernel: 32-bit buffer addressing of the operand where its rows span < 2 GiB
     int64_t lean = 1;        // 1: the lean gather kernel (32-float panels, 32-row tiles) wherever it applies,
                              // 0: the generic kernel everywhere (row-major operands only)
-    int64_t ids16 = 1;       // stream neighbour ids as 16-bit values when the graph allows it
+    int64_t ids16 = 1;       // stream neighbour ids as 16-bit values when the graph allows it (the gather kernel's col16 and
+                             // the one-launch plan's dcols / sids streams); 0: 32-bit ids at any size
     int64_t sym_desc = 1;    // upper-triangle leg 2: an XCD takes its panels in descending order — the big ones (N/128
                              // workgroups: one panel at a time in its L2) first, the small ones as the tail: leg 2 -4.7 %
     int64_t ev_tri = 1;      // evidence counts of a whole square block: paths to b >= a only + a mirror pass (round 4)
@@ -96,7 +97,14 @@ struct Tuning {
                              // the 256-byte-per-column fragment image and its upload on power-law graphs (8 ms at N = 65536)
     int64_t dense_sym = -1;  // dense part in the upper-triangle form of leg 2: 1 yes, 0 no, -1 = when the
                              // dense sets hold at least half of the pattern's entries
+    int64_t restrict_support = -1;  // SimRank++ leg 2 restricted to supp(E) (gather3's RESTRICT instantiations: a lane group
+                             // whose 32 evidence counts are all zero skips its gathers), decided when a plan is created:
+                             // 1 always (evidence given), 0 never, -1 when fewer than half of the 32-column segments are live
 };
+// a plan's choice of the restricted leg 2 from its live / total evidence segments (tuning "restrict_support")
+inline int32_t restrict_choice(const Tuning& t, int64_t live, int64_t total) {
+    return t.restrict_support < 0 ? (2 * live < total ? 1 : 0) : int32_t(t.restrict_support != 0);
+}
 Tuning& tuning();            // the process-wide defaults: simrank_set_tuning writes them, simrank_graph_create
 Tuning tuning_snapshot();    // copies them (under a lock) into the graph it builds; launches read the copy
 

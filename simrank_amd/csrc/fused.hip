@@ -825,7 +825,7 @@ int build_fused_plan(simrank_graph* g, const int32_t* rowptr, const int32_t* col
     // — BASELINE config 5 — would need that one column kept out of the streams: forcing it into the dense set of every
     // block that references it was tried and made config 5 slower, the column being a hub that nearly every block
     // references; what 16-bit ids are worth was measured at config 4: 1.3-2.7 % of leg 1.)
-    const bool ids16 = K <= 65535;
+    const bool ids16 = K <= 65535 && g->tun.ids16;
     std::vector<int32_t> blk_quad0(size_t(nblk) + 1, 0);
     std::vector<int32_t> dcols;                       // padded to 64 per block
     std::vector<uint32_t> abits;                      // [quad][lane][4 steps]

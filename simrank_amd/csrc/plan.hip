@@ -259,7 +259,7 @@ int simrank_plan_create(int64_t n, int64_t nnz, const int32_t* rowptr, const int
         int64_t live = 0, total = 1;
         rc = simrank_evidence_live_segments(p->ev, 32, p->rows_pad, n, n, &live, &total, p->stream);
         if (rc) return fail(rc);
-        p->restrict_support = 2 * live < total ? 1 : 0;
+        p->restrict_support = restrict_choice(p->g->tun, live, total);
     }
     if (opt->apriori) {
         // host n x n (caller's order) -> device row-major -> panel-blocked in the solver's order
@@ -548,6 +548,13 @@ int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* updates, const
     if (n) *n = p->n;
     if (updates) *updates = p->updates;
     if (graph) *graph = p->g;
+    return SIMRANK_OK;
+}
+
+int simrank_plan_get(const simrank_plan* p, const char* key, int64_t* value) {
+    SR_REQUIRE(p && key && value, "NULL argument");
+    if (!strcmp(key, "restrict_support")) *value = p->restrict_support;
+    else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }
 

@@ -1098,7 +1098,7 @@ static int create_side(const SideIn& in, simrank_comm* comm, void* stream, simra
             int64_t live = 0, total = 1;
             rc = simrank_evidence_live_segments(p->ev, p->ld_ev, 0, n, p->Lm, &live, &total, p->stream);
             if (rc) return fail(rc);
-            p->restrict_support = 2 * live < total ? 1 : 0;
+            p->restrict_support = restrict_choice(p->g->tun, live, total);
         }
     }
     if (in.apriori && p->Lm) {
@@ -1510,6 +1510,13 @@ int simrank_shardplan_info(const simrank_shardplan* p, int64_t* n, int64_t* col_
     return SIMRANK_OK;
 }
 
+int simrank_shardplan_get(const simrank_shardplan* p, const char* key, int64_t* value) {
+    SR_REQUIRE(p && key && value, "NULL argument");
+    if (!strcmp(key, "restrict_support")) *value = p->restrict_support;
+    else SR_REQUIRE(false, "unknown plan key '%s'", key);
+    return SIMRANK_OK;
+}
+
 
 }  // extern "C"
 
@@ -1659,7 +1666,7 @@ int simrank_shardbiplan_create(int64_t n1, int64_t n2, int64_t nnz, const int32_
             int64_t live = 0, total = 1;
             rc = simrank_evidence_live_segments(p->ev, p->ld_ev, 0, p->n, p->Lm, &live, &total, p->stream);
             if (rc) return fail(rc);
-            p->restrict_support = 2 * live < total ? 1 : 0;
+            p->restrict_support = restrict_choice(p->g->tun, live, total);
         }
     }
     bp->side[0]->src = bp->side[1];

@@ -181,6 +181,12 @@ class Plan:
         check(self.ops.lib.simrank_plan_info(self.handle, None, None, C.byref(g)), "simrank_plan_info")
         return g
 
+    def get(self, key: str) -> int:
+        """What the plan chose when it was created (simrank_plan_get): "restrict_support"."""
+        v = C.c_int64(0)
+        check(self.ops.lib.simrank_plan_get(self.handle, key.encode(), C.byref(v)), f"simrank_plan_get({key})")
+        return v.value
+
     def evidence_counts(self) -> np.ndarray:
         """uint8 [n, n] common in-neighbour counts (saturated at 255) in the caller's order."""
         out = np.empty((self.n, self.n), dtype=np.uint8)
@@ -239,6 +245,13 @@ class ShardPlanOptions(C.Structure):           # struct simrank_shardplan_option
                 ("wire_fp16", C.c_int32), ("storage_fp16", C.c_int32)]
 
 
+def _shardplan_get(lib, handle, key: str) -> int:
+    """What a sharded plan (or a side of a sharded bipartite one) chose when it was created (simrank_shardplan_get)."""
+    v = C.c_int64(0)
+    check(lib.simrank_shardplan_get(handle, key.encode(), C.byref(v)), f"simrank_shardplan_get({key})")
+    return v.value
+
+
 class ShardPlans:
     """This process's share of a SHARDED fit behind the C ABI (simrank_shardplan_*: K10, S split by column block over
     ``world`` ranks): ONE plan when ``comm`` is an RCCL communicator of a multi-process world (``rccl_comm``), or all
@@ -295,7 +308,7 @@ class ShardPlans:
         check(self.ops.lib.simrank_shardplan_info(self.plans[i], C.byref(n), C.byref(lo), C.byref(hi), C.byref(half),
                                                   C.byref(stages), C.byref(updates)), "simrank_shardplan_info")
         return dict(n=n.value, col_lo=lo.value, col_hi=hi.value, half_form=bool(half.value), stages=stages.value,
-                    updates=updates.value)
+                    updates=updates.value, restrict_support=_shardplan_get(self.ops.lib, self.plans[i], "restrict_support"))
 
     TIMING_KEYS = ("leg1_ms", "exchange1_ms", "wait_before_leg2_ms", "leg2_ms", "count_and_exchange2_ms", "update_ms")
 
@@ -484,7 +497,8 @@ class ShardBiPlans:
         check(self.ops.lib.simrank_shardplan_info(C.c_void_p(self._sides[group][i]), C.byref(n), C.byref(lo), C.byref(hi),
                                                   C.byref(half), C.byref(stages), C.byref(updates)), "simrank_shardplan_info")
         return dict(n=n.value, col_lo=lo.value, col_hi=hi.value, half_form=bool(half.value), stages=stages.value,
-                    updates=updates.value)
+                    updates=updates.value,
+                    restrict_support=_shardplan_get(self.ops.lib, C.c_void_p(self._sides[group][i]), "restrict_support"))
 
     def result(self, group: int, root: int = 0, i_am_root: bool = True):
         """Group 1 | 2's whole matrix (float64, caller's order) on rank ``root``; None elsewhere.  Collective."""
@@ -591,6 +605,12 @@ class BiPlan:
         check(self.ops.lib.simrank_biplan_topk(self.handle, int(group), int(k), int(exclude_diag), idx.ctypes.data,
                                                val.ctypes.data), "simrank_biplan_topk")
         return idx, val
+
+    def get(self, group: int, key: str) -> int:
+        """What group 1 | 2's side chose when the plan was created (simrank_biplan_get): "restrict_support"."""
+        v = C.c_int64(0)
+        check(self.ops.lib.simrank_biplan_get(self.handle, int(group), key.encode(), C.byref(v)), f"simrank_biplan_get({key})")
+        return v.value
 
     def evidence_counts(self, group: int) -> np.ndarray:
         """uint8 [n, n] counts gating group 1 | 2's update, caller's order."""
@@ -1075,6 +1095,13 @@ class HipOps:
         check(self.lib.simrank_graph_fused_stats(g.handle, C.byref(a), C.byref(b), C.byref(c)),
               "simrank_graph_fused_stats")
         return a.value, b.value, c.value
+
+    def graph_get(self, g, key: str) -> int:
+        """What a graph (a ``Graph``, or the handle of a plan's graph) chose when it was built (simrank_graph_get):
+        "fused_ids16" (-1: no one-launch plan), "gather_ids16"."""
+        v = C.c_int64(0)
+        check(self.lib.simrank_graph_get(getattr(g, "handle", g), key.encode(), C.byref(v)), f"simrank_graph_get({key})")
+        return v.value
 
     def dense_part(self, g: Graph, X: Matrix, n_cols: int | None = None):
         """The matrix-core part of ``spmm`` alone (measurement; see simrank_dense_part)."""

@@ -29,9 +29,9 @@ def test_library_exports_every_declared_symbol():
     assert exported == _declared()          # nothing else leaks out (-fvisibility=hidden)
 
 
-def test_abi_version_and_error_string():
+def test_abi_version_8_and_error_string():
     lib = _lib.load()
-    assert lib.simrank_abi_version() == 7
+    assert lib.simrank_abi_version() == 8
     rc = lib.simrank_set_tuning(b"no_such_knob", 1)
     assert rc == -1 and b"no_such_knob" in lib.simrank_last_error()
     assert lib.simrank_set_tuning(b"panel", 48) == -1
@@ -45,6 +45,54 @@ def test_abi_version_and_error_string():
     v = ctypes.c_int64(-7)
     assert lib.simrank_get_tuning(b"fuse_min", ctypes.byref(v)) == 0 and v.value == 0
     assert lib.simrank_graph_set_dense_terms(None, 3) == -1
+
+
+def test_restrict_support_key_round_trips_and_refuses_other_values():
+    """Tuning "restrict_support" (ABI 8): -1 (automatic, the default), 0 (never) and 1 (always) round-trip, 2 and -2 are
+    refused with a message and leave the value as it was."""
+    lib = _lib.load()
+    v = ctypes.c_int64(7)
+    assert lib.simrank_get_tuning(b"restrict_support", ctypes.byref(v)) == 0 and v.value == -1
+    try:
+        for x in (0, 1, -1):
+            assert lib.simrank_set_tuning(b"restrict_support", x) == 0
+            assert lib.simrank_get_tuning(b"restrict_support", ctypes.byref(v)) == 0 and v.value == x
+        assert lib.simrank_set_tuning(b"restrict_support", 1) == 0
+        for bad in (2, -2):
+            assert lib.simrank_set_tuning(b"restrict_support", bad) == -1
+            assert b"restrict_support" in lib.simrank_last_error()
+            assert lib.simrank_get_tuning(b"restrict_support", ctypes.byref(v)) == 0 and v.value == 1
+    finally:
+        assert lib.simrank_set_tuning(b"restrict_support", -1) == 0
+
+
+_GETTERS = {"simrank_plan_get": "plan", "simrank_biplan_get": "plan", "simrank_shardplan_get": "plan",
+            "simrank_graph_get": "graph"}
+
+
+def test_choice_getters_are_exported_and_declared():
+    lib = ctypes.CDLL(_lib.LIB_PATH)
+    for name in _GETTERS:
+        assert name in _declared() and name in _lib.PROTOTYPES, name
+        assert hasattr(lib, name), name
+    assert len(_declared()) == 117
+
+
+@pytest.mark.parametrize("name", sorted(_GETTERS))
+def test_choice_getters_refuse_a_null_handle_and_an_unknown_key(name):
+    """Each getter returns -1 with a message for a NULL handle (known key or not) and for a NULL key or value; the value it
+    was given stays untouched.  (An unknown key on a live handle: make asan's driver for the graph, the GPU suite for the
+    plans — tests/test_gpu_restricted.py.)"""
+    lib = _lib.load()
+    fn = getattr(lib, name)
+    head = (None, 1) if name == "simrank_biplan_get" else (None,)
+    keys = [b"restrict_support"] if _GETTERS[name] == "plan" else [b"fused_ids16", b"gather_ids16"]
+    for key in keys + [b"no_such_key"]:
+        v = ctypes.c_int64(-7)
+        assert fn(*head, key, ctypes.byref(v)) == -1
+        assert b"NULL" in lib.simrank_last_error(), (name, key)
+        assert v.value == -7
+    assert fn(*head, keys[0], None) == -1 and b"NULL" in lib.simrank_last_error()
 
 
 def test_host_logic_under_the_sanitizers():
@@ -76,7 +124,7 @@ def test_product_path_fails_loudly_without_gpu():
         SRA.SimRank().fit(pd.DataFrame({"from": [1, 2], "to": [2, 1]}), verbose=False)
 
 
-def test_header_is_plain_c_and_a_c_program_links(tmp_path):
+def test_header_is_plain_c_and_a_c_program_links_at_abi_8(tmp_path):
     """The boundary is a C ABI: the header compiles as C99 with no other include path, and a C
     program linked against the shared library can call it (argument checks only: no device)."""
     import os
@@ -118,4 +166,4 @@ int main(void) {
                         capture_output=True, text=True)
     assert cc.returncode == 0, cc.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert run.returncode == 0 and "abi 7 ok" in run.stdout, (run.returncode, run.stdout, run.stderr)
+    assert run.returncode == 0 and "abi 8 ok" in run.stdout, (run.returncode, run.stdout, run.stderr)

@@ -23,7 +23,7 @@ def ops():
     o.set_tuning(fuse_steps=1, fuse_min=2)   # small test graphs: a dense set however few steps it makes
     yield o
     o.set_tuning(fuse=1, fuse_min=0, fuse_steps=-1, fuse_unit=48, fuse_group=3, fuse_shards=1, fuse_rows=8192, fuse_order=0,
-                 fuse_sym=-1)
+                 fuse_sym=-1, ids16=1)
 
 
 @contextlib.contextmanager
@@ -33,7 +33,7 @@ def knobs(ops, **kw):
         yield
     finally:
         ops.set_tuning(fuse=1, fuse_min=2, fuse_steps=1, fuse_unit=48, fuse_group=3, fuse_shards=1, fuse_rows=8192, fuse_order=0,
-                       fuse_sym=-1)
+                       fuse_sym=-1, ids16=1)
 
 
 def put_blocked(ops, a, dtype=np.float32):
@@ -302,8 +302,9 @@ def test_fused_leg1_on_a_sharded_ranks_operand(ops, shape, tb, pad):
 # tile; second `.dot` of SimRank.py:139 / :298 / :361 / :420, the element-wise lines :140, :316, :362, :453, the count of :74
 # ---------------------------------------------------------------------------------------------------------------------
 def _leg2_case(ops, n, variant, seed, **graph_knobs):
-    """-> (result, exact count, count_any count, float64 reference, previous iterate): a symmetric product (Tt = (W S)^T of a
-    symmetric S), symmetric counts / prior, through the epilogue with `symmetric=True` on panel-blocked matrices."""
+    """-> (result, exact count, count_any count, float64 reference, previous iterate, (steps, covered, remainder, id width of
+    the one-launch plan)): a symmetric product (Tt = (W S)^T of a symmetric S), symmetric counts / prior, through the epilogue
+    with `symmetric=True` on panel-blocked matrices."""
     csr = corner_csr(n, n, seed=seed, hubs=min(n, 150))
     rng = np.random.default_rng(seed)
     W = dense64(csr)
@@ -331,6 +332,7 @@ def _leg2_case(ops, n, variant, seed, **graph_knobs):
     with knobs(ops, **graph_knobs):
         g = ops.graph(csr)
         steps, cov, rem = ops.fused_stats(g)
+        fused16 = ops.graph_get(g, "fused_ids16")
         y = ops.matrix(n, n, blocked=True)
         ep = dict(coef=0.8, previous=put_blocked(ops, prev), eps=0.05, diag_col0=0, symmetric=True, lbd=lbd,
                   evidence=None if cnt is None else put_blocked(ops, cnt, np.uint8),
@@ -341,7 +343,7 @@ def _leg2_case(ops, n, variant, seed, **graph_knobs):
         ops.spmm(g, put_blocked(ops, Tt), y2, epilogue=dict(ep, count_any=True))
         assert np.array_equal(ops.download(y2), got)
         some = ops.read_changed()
-    return got, exact, some, want, prev, (steps, cov, rem)
+    return got, exact, some, want, prev, (steps, cov, rem, fused16)
 
 
 @pytest.mark.parametrize("n", [64, 129, 200, 520, 1000, 1031, 2100])
@@ -365,6 +367,23 @@ def test_fused_leg2_epilogue_triangle_and_mirror(ops, n, variant):
     assert abs(exact - exact0) <= 4                                 # (elements within rounding of eps may fall either way)
 
 
+@pytest.mark.parametrize("n", [64, 1031, 2100])
+@pytest.mark.parametrize("variant", ["plain", "all"])
+def test_fused_leg2_with_32_bit_ids(ops, n, variant):
+    """fused_trans_kernel<…, IDS16 = false, SYM> (tuning ids16 = 0: 32-bit dcols / sids streams at any size): against float64,
+    and bit-equal to the 16-bit run with the same exact count — only the width of the ids differs, not the order of the sums.
+    (count_any's number depends on when the waves see each other's counters: it is checked for what it promises, non-zero
+    exactly when the exact count is.)"""
+    got, exact, some, want, prev, stats = _leg2_case(ops, n, variant, seed=n, fuse_sym=1, ids16=0)
+    assert stats[1] > 0 and stats[3] == 0
+    np.testing.assert_allclose(got, want, rtol=RTOL, atol=1e-30)
+    assert exact == int((np.abs(got.astype(np.float64) - prev.astype(np.float64)) > 0.05).sum())
+    got16, exact16, some16, _, _, stats16 = _leg2_case(ops, n, variant, seed=n, fuse_sym=1)
+    assert stats16[3] == 1 and stats16[:3] == stats[:3]
+    assert np.array_equal(got, got16)
+    assert exact == exact16 and 0 < some <= exact and 0 < some16 <= exact16
+
+
 @pytest.mark.parametrize("split", [dict(fuse_unit=4, fuse_rows=400), dict(fuse_group=1), dict(fuse_group=4, fuse_min=4)])
 def test_fused_leg2_with_split_blocks_and_grouped_units(ops, split):
     """Blocks cut into matrix-core units and gather units (the last arriver combines, scales, runs the epilogue and stores),
@@ -373,6 +392,18 @@ def test_fused_leg2_with_split_blocks_and_grouped_units(ops, split):
     np.testing.assert_allclose(got, want, rtol=RTOL, atol=1e-30)
     assert np.array_equal(got[:128, 128:], got[128:, :128].T)
     assert exact == int((np.abs(got.astype(np.float64) - prev.astype(np.float64)) > 0.05).sum()) and 0 < some <= exact
+
+
+def test_fused_leg2_with_split_blocks_and_32_bit_ids(ops):
+    """Split blocks (matrix-core and gather units) with 32-bit id streams: the values and the exact count of the 16-bit run,
+    bit for bit."""
+    split = dict(fuse_sym=1, fuse_min=3, fuse_steps=2, fuse_unit=4, fuse_rows=400)
+    got, exact, some, want, prev, stats = _leg2_case(ops, 2600, "all", seed=77, ids16=0, **split)
+    assert stats[3] == 0
+    np.testing.assert_allclose(got, want, rtol=RTOL, atol=1e-30)
+    got16, exact16, some16, _, _, stats16 = _leg2_case(ops, 2600, "all", seed=77, **split)
+    assert stats16[3] == 1 and np.array_equal(got, got16) and exact == exact16
+    assert 0 < some <= exact and 0 < some16 <= exact16
 
 
 def test_fused_leg2_runs_the_bipartite_plan_where_the_dense_sets_dominate(ops):
@@ -396,3 +427,24 @@ def test_fused_leg2_runs_the_bipartite_plan_where_the_dense_sets_dominate(ops):
         np.testing.assert_allclose(s1, want["S1"], rtol=RTOL, atol=1e-30)
         np.testing.assert_allclose(s2, want["S2"], rtol=RTOL, atol=1e-30)
         bp.free()
+
+
+def test_fused_leg2_with_32_bit_ids_through_the_bipartite_fit(ops):
+    """The MovieLens-shaped BipartiteSimRankPP fit of the test above through the shipped loop with tuning ids16 = 0 (default
+    fuse_sym: both legs the one-launch kernel, its id streams 32-bit): the oracle's values, and the bits of the ids16 = 1 fit."""
+    import simrank_amd.SimRank as SRA
+    from oracle import simrank_oracle as O
+    from tests.graphs import bipartite_random
+    df = bipartite_random(1400, 900, 0.12, seed=1400)
+    want = O.fit_bipartite_pp(df, verbose=False, strict_reference=False)
+    out = {}
+    for ids16 in (0, 1):
+        with knobs(ops, fuse_min=0, fuse_pays=-1, fuse_steps=-1, ids16=ids16):      # (the library's defaults but ids16)
+            est = SRA.BipartiteSimRankPP()
+            s1, s2 = est.fit(df, verbose=False, strict_reference=False)
+        assert list(s1.index) == want["sorted1"] and list(s2.index) == want["sorted2"]
+        np.testing.assert_allclose(s1.values, want["S1"], rtol=RTOL, atol=1e-30)
+        np.testing.assert_allclose(s2.values, want["S2"], rtol=RTOL, atol=1e-30)
+        assert est.converged_at == want["k"]
+        out[ids16] = (s1.values, s2.values)
+    assert np.array_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1])

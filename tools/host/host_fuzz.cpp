@@ -451,6 +451,7 @@ int main(int argc, char** argv) {
         simrank_set_tuning("fuse", it % 2 ? 2 : 1);
 #endif
         simrank_set_tuning("fuse_cap", it % 3 == 0 ? 1000 : (it % 3 == 1 ? 3000 : 1 << 30));
+        simrank_set_tuning("ids16", it % 5 == 2 ? 0 : 1);                 // (0: 32-bit ids at any size, both plans)
         // (every 17th graph has no entries at all: plans of nothing but empty rows)
         Csr c = random_graph(rng, M, K, it % 17 == 16 ? 0.0 : 1 + u(rng) * 12, it % 17 == 16 ? 0 : int(u(rng) * 200),
                              u(rng), it % 2 == 0);
@@ -475,6 +476,18 @@ int main(int argc, char** argv) {
         int64_t steps = 0, cov = 0, rem = 0;
         simrank_graph_fused_stats(g, &steps, &cov, &rem);
         CHECK(cov + rem == (int64_t)c.col.size(), "fused stats");
+        {
+            // simrank_graph_get: the id widths the graph chose, as the knob and the column count allow; unknown keys refused
+            int64_t v = -7;
+            const bool ids16 = it % 5 != 2;
+            CHECK(simrank_graph_get(g, "fused_ids16", &v) == SIMRANK_OK &&
+                      v == (g->fused ? int64_t(ids16 && c.K <= 65535) : int64_t(-1)), "graph_get fused_ids16 = %lld", (long long)v);
+            CHECK(simrank_graph_get(g, "gather_ids16", &v) == SIMRANK_OK && v == int64_t(ids16 && g->col16 != nullptr),
+                  "graph_get gather_ids16 = %lld", (long long)v);
+            v = -7;
+            CHECK(simrank_graph_get(g, "no_such_key", &v) == SIMRANK_ERR_INVALID && v == -7 &&
+                      strstr(simrank_last_error(), "no_such_key"), "graph_get: unknown key accepted");
+        }
         simrank_graph_destroy(g);
         // malformed input must be refused, not read out of bounds
         if (c.col.size() > 2) {
@@ -486,6 +499,7 @@ int main(int argc, char** argv) {
     }
     // launch orders that put other units between the units of a split block (fuse_order > 0): graphs with many blocks, some
     // split into matrix-core and gather units, many not
+    simrank_set_tuning("ids16", 1);
     for (int order : {1, 2, 3}) {
         simrank_set_tuning("fuse", 1);
         simrank_set_tuning("fuse_min", 3);
