@@ -479,7 +479,19 @@ SIMRANK_API int simrank_plan_leg_times(simrank_plan* p, double* leg1_ms, double*
 SIMRANK_API int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* updates, const simrank_graph** graph);
 /* what the plan chose when it was created, by key: "restrict_support" 1 | 0 leg 2 is restricted to supp(E) (tuning
  * "restrict_support").  SIMRANK_ERR_INVALID for a NULL handle or an unknown key.  (ABI 8; likewise simrank_biplan_get
- * per group 1 | 2 and simrank_shardplan_get, which also serves the sides of a sharded bipartite plan) */
+ * per group 1 | 2 and simrank_shardplan_get, which also serves the sides of a sharded bipartite plan)
+ * What a reader of the CURRENT iterate needs (the result queries of include/simrank_select.h read it in place; valid
+ * until the next update, reset, trim or destroy):
+ *      "iterate"         device address of S[cur] (0 after simrank_plan_trim)
+ *      "iterate_layout"  0: f32 panel-blocked (32-column panels), 2: fp16-held (value x 2^14, 64-column panels)
+ *      "iterate_stride"  rows_pad of the panels
+ *      "iterate_rows"    n (rows in the solver's order)
+ *      "iterate_col_lo" / "iterate_col_hi"  0 / n (the columns the plan holds, solver's order)
+ *      "ids"             device address of n int32: the caller's node id at each solver position (rows and columns)
+ * simrank_biplan_get answers the same keys per group (layout 0).  simrank_shardplan_get answers them for the rank's
+ * column block: layout 1 (f32 row-major, "iterate_stride" = ld) or 2 (fp16-held, "iterate_stride" = rows_pad), n rows,
+ * columns [col_lo, col_hi) of the solver's order; the block's column ids are "ids" + col_lo (the same values as
+ * simrank_shardplan_columns). */
 SIMRANK_API int simrank_plan_get(const simrank_plan* p, const char* key, int64_t* value);
 SIMRANK_API int simrank_plan_destroy(simrank_plan* p);
 
@@ -528,6 +540,7 @@ SIMRANK_API int simrank_biplan_topk(simrank_biplan* p, int32_t group, int32_t k,
 SIMRANK_API int simrank_biplan_rows_f32(simrank_biplan* p, int32_t group, const int32_t* rows, int32_t n_rows, float* dst,
                                         int64_t ld);
 SIMRANK_API int simrank_biplan_evidence_u8(simrank_biplan* p, int32_t group, uint8_t* dst, int64_t ld);
+/* simrank_plan_get's keys, per group 1 | 2 (every group's iterate is f32 panel-blocked, layout 0) */
 SIMRANK_API int simrank_biplan_get(const simrank_biplan* p, int32_t group, const char* key, int64_t* value);
 SIMRANK_API int simrank_biplan_trim(simrank_biplan* p);
 SIMRANK_API int simrank_biplan_destroy(simrank_biplan* p);
@@ -624,6 +637,8 @@ SIMRANK_API int simrank_shardplan_set_timing(simrank_shardplan* p, int32_t updat
 SIMRANK_API int simrank_shardplan_timings(simrank_shardplan* p, double* ms, int32_t n_ms, int32_t* updates);
 SIMRANK_API int simrank_shardplan_info(const simrank_shardplan* p, int64_t* n, int64_t* col_lo, int64_t* col_hi,
                                        int32_t* half_form, int32_t* stages, int32_t* updates);
+/* simrank_plan_get's keys for this rank's column block: "iterate_layout" 1 (f32 row-major, "iterate_stride" = ld) or 2
+ * (fp16-held, "iterate_stride" = rows_pad); "iterate_col_lo" / "iterate_col_hi" the block's columns; "ids" the whole order */
 SIMRANK_API int simrank_shardplan_get(const simrank_shardplan* p, const char* key, int64_t* value);
 SIMRANK_API int simrank_shardplan_destroy(simrank_shardplan* p);
 

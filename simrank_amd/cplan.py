@@ -2,7 +2,7 @@
 
 ``PlanSolver`` gives ``engine.Plan`` (``simrank_plan_*``: SimRank.py:129-141, :351-363, :443-455) and ``engine.BiPlan``
 (``simrank_biplan_*``: :288-303, :410-425, :478-493) the few methods ``estimators.py`` asks of a solver — ``run`` with
-the reference's console hooks, ``result``, ``topk``, ``evidence``, ``release`` — so that what a user imports runs the
+the reference's console hooks, ``result``, ``topk``, ``pairs``, ``evidence``, ``release`` — so that what a user imports runs the
 fastest loop the library has: both legs and the count of an update queued by one C call, update k + 1 queued before the
 count of update k is read on small graphs, and a banded hand-back (csrc/handback.hip: full form by default; the
 upper-triangle form is opt-in, ``SIMRANK_SYM_HANDBACK=1``, and checks on the device that the result is symmetric).
@@ -117,6 +117,11 @@ class PlanSolver:
         k = int(min(k, max(1, n - (1 if exclude_diag else 0))))
         idx, val = self.plan.topk(j + 1, k, exclude_diag) if self.bipartite else self.plan.topk(k, exclude_diag)
         return idx, val.astype(np.float64)
+
+    def pairs(self, j, t, max_pairs):
+        """Side j's pairs at least ``t`` similar, selected on the device: (offsets [n + 1], neighbour ids, float32 values)
+        in the caller's order (``Plan.pairs_above``)."""
+        return self.plan.pairs_above(j + 1, t, max_pairs) if self.bipartite else self.plan.pairs_above(t, max_pairs)
 
     def evidence(self, j=0):
         """Evidence matrix of side j (1 - 0.5**count, SimRank.py:316) as float64 in the caller's node order."""

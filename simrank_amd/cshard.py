@@ -4,7 +4,7 @@ more than one rank (BASELINE.json config 5 in its stated form: N = 65536 SimRank
 The Python driver's solver keeps fp16-held matrices to one rank; the sharded loop on such matrices lives behind the C ABI
 (``simrank_shardplan_*``, csrc/shardplan.hip: leg 1 and a full-form leg 2 of half.hip on every rank's column block, the fp16
 panels themselves on the links).  ``CShardSolver`` gives that loop the few methods the estimators ask of a solver —
-``run`` with the reference's progress callbacks (SimRank.py:129-140), ``result``, ``topk``, ``release`` — over
+``run`` with the reference's progress callbacks (SimRank.py:129-140), ``result``, ``topk``, ``pairs``, ``release`` — over
 
 * ``LocalWorld(P)``: an in-process group of P virtual ranks on one device (tests, single-GPU emulation), or
 * ``TorchWorld`` on RCCL ranks: the library's own RCCL communicator, made from an id rank 0 broadcasts through
@@ -194,6 +194,35 @@ class CShardSolver:
         if not isinstance(self.world, LocalWorld):
             idx, val = self._share((idx, val))
         return idx, val.astype(np.float64)
+
+    def pairs(self, j, t, max_pairs):
+        """Side j's pairs at least ``t`` similar (``engine.Selection``): every rank counts and emits the hits of its own
+        columns; an in-process group merges them here, an RCCL world agrees on the total (``max_pairs`` is refused on every
+        rank alike) and sends the pieces to rank 0, sizes first, which merges them.  Delivered as ``result``."""
+        from . import _select
+        sel = self.plans.selection(j + 1, t) if self.bipartite else self.plans.selection(t)
+        if isinstance(self.world, LocalWorld):
+            if sel.total > max_pairs:
+                raise _select.too_many(sel.total, max_pairs)
+            return sel.pairs()
+        dist, group = self.world.dist, self.world.group
+        sizes = [None] * self.world.size
+        dist.all_gather_object(sizes, sel.total, group=group)
+        total = sum(sizes)
+        if total > max_pairs:
+            raise _select.too_many(total, max_pairs)
+        pieces = [None] * self.world.size if self.root else None
+        dist.gather_object(sel.emit(), pieces, dst=dist.get_global_rank(group, 0) if group is not None else 0,
+                           group=group)
+        out = _select.merge([p for got in pieces for p in got], sel.row_order) if self.root else None
+        if getattr(self.world, "handback", "root") == "root":
+            if not self.root:
+                import warnings
+                warnings.warn("TorchWorld(handback='root'): only rank 0 receives the similarity matrix, fit() returns "
+                              "None on this rank (pass handback='all', or fit(top_k=k), to get results on every rank)",
+                              RuntimeWarning, stacklevel=4)
+            return out
+        return self._share(out)
 
     def release(self):
         self.plans.free()

@@ -37,6 +37,7 @@ struct side_t {
     uint8_t* ev = nullptr;
     float* prior = nullptr;
     int32_t* inv = nullptr;                    // device: position of caller's node i in the solver's order
+    int32_t* ord_dev = nullptr;                // device: caller's node at position r (simrank_biplan_get "ids")
     float coef = 0.8f, lbd = 0.f;
     int32_t restrict_support = 0;
     int cur = 0;
@@ -135,7 +136,7 @@ int simrank_biplan_destroy(simrank_biplan* p) {
     if (p->stream) (void)hipStreamSynchronize(p->stream);
     for (side_t& a : p->s) {
         (void)pool_free(a.S[0]); (void)pool_free(a.S[1]); (void)pool_free(a.Tt); (void)pool_free(a.ev);
-        (void)pool_free(a.prior); (void)pool_free(a.inv);
+        (void)pool_free(a.prior); (void)pool_free(a.inv); (void)pool_free(a.ord_dev);
         simrank_graph_destroy(a.g);
     }
     (void)pool_free(p->counters);
@@ -260,6 +261,8 @@ int simrank_biplan_create(int64_t n1, int64_t n2, int64_t nnz, const int32_t* ro
         BIPLAN_HIP(pool_hip_alloc((void**)&a.Tt, a.t_bytes));
         BIPLAN_HIP(pool_hip_alloc((void**)&a.inv, size_t(a.n) * sizeof(int32_t)));
         BIPLAN_HIP(hipMemcpyAsync(a.inv, inv[w].data(), size_t(a.n) * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
+        BIPLAN_HIP(pool_hip_alloc((void**)&a.ord_dev, size_t(a.n) * sizeof(int32_t)));
+        BIPLAN_HIP(hipMemcpyAsync(a.ord_dev, ord[w].data(), size_t(a.n) * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
         BIPLAN_HIP(hipStreamSynchronize(p->stream));
         const bool q2 = opt->evidence && opt->strict_reference && w == 1;      // Evidence_N1 on the group-2 update
         if (q2 && n1 != n2 && n1 != 1) {
@@ -502,6 +505,12 @@ int simrank_biplan_get(const simrank_biplan* p, int32_t group, const char* key, 
     SR_REQUIRE(group == 1 || group == 2, "group must be 1 or 2");
     const side_t& a = p->s[group - 1];
     if (!strcmp(key, "restrict_support")) *value = a.restrict_support;
+    else if (!strcmp(key, "iterate")) *value = (int64_t)(uintptr_t)a.S[a.cur];
+    else if (!strcmp(key, "iterate_layout")) *value = 0;
+    else if (!strcmp(key, "iterate_stride")) *value = a.rows_pad;
+    else if (!strcmp(key, "iterate_rows") || !strcmp(key, "iterate_col_hi")) *value = a.n;
+    else if (!strcmp(key, "iterate_col_lo")) *value = 0;
+    else if (!strcmp(key, "ids")) *value = (int64_t)(uintptr_t)a.ord_dev;
     else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }

@@ -554,6 +554,12 @@ int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* updates, const
 int simrank_plan_get(const simrank_plan* p, const char* key, int64_t* value) {
     SR_REQUIRE(p && key && value, "NULL argument");
     if (!strcmp(key, "restrict_support")) *value = p->restrict_support;
+    else if (!strcmp(key, "iterate")) *value = (int64_t)(uintptr_t)p->S[p->cur];
+    else if (!strcmp(key, "iterate_layout")) *value = p->half ? 2 : 0;
+    else if (!strcmp(key, "iterate_stride")) *value = p->rows_pad;
+    else if (!strcmp(key, "iterate_rows") || !strcmp(key, "iterate_col_hi")) *value = p->n;
+    else if (!strcmp(key, "iterate_col_lo")) *value = 0;
+    else if (!strcmp(key, "ids")) *value = (int64_t)(uintptr_t)p->ord_dev;
     else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }

@@ -400,6 +400,7 @@ struct simrank_shardplan {
     float* prior = nullptr;
     int32_t* inv = nullptr;                 // device: position of caller's node i in the solver's order
     std::vector<int32_t> ord;               // host: ord[position] = caller's node
+    int32_t* ord_dev = nullptr;             // device copy of ord (simrank_shardplan_get "ids")
     unsigned long long* counters = nullptr;
     unsigned long long* host_counters[2] = {nullptr, nullptr};
     hipEvent_t counted[2] = {nullptr, nullptr};
@@ -922,7 +923,7 @@ int simrank_shardplan_destroy(simrank_shardplan* p) {
     for (void* b : {(void*)p->S[0], (void*)p->S[1], (void*)p->send, (void*)p->recv, (void*)p->sh_send, (void*)p->sh_recv,
                     (void*)p->wire[0], (void*)p->wire[1], (void*)p->wire[2], (void*)p->wire[3], (void*)p->wire[4],
                     (void*)p->wire[5], (void*)p->ev,
-                    (void*)p->prior, (void*)p->inv, (void*)p->counters, (void*)p->hand[0], (void*)p->hand[1], (void*)p->send2,
+                    (void*)p->prior, (void*)p->inv, (void*)p->ord_dev, (void*)p->counters, (void*)p->hand[0], (void*)p->hand[1], (void*)p->send2,
                     (void*)p->recv2})
         (void)pool_free(b);
     for (int i = 0; i < 2; ++i) {
@@ -1084,6 +1085,8 @@ static int create_side(const SideIn& in, simrank_comm* comm, void* stream, simra
     }
     SP_HIP(dev((void**)&p->inv, size_t(n) * 4));
     SP_HIP(hipMemcpyAsync(p->inv, inv.data(), size_t(n) * 4, hipMemcpyHostToDevice, p->stream));
+    SP_HIP(dev((void**)&p->ord_dev, size_t(n) * 4));
+    SP_HIP(hipMemcpyAsync(p->ord_dev, p->ord.data(), size_t(n) * 4, hipMemcpyHostToDevice, p->stream));
     SP_HIP(hipStreamSynchronize(p->stream));             // (inv may be a host vector about to go away)
     if (in.evidence && p->Lm) {
         // common in-neighbour counts of the rank's columns (SimRank.py:311-320), 1 - 2^-count in the epilogue
@@ -1513,6 +1516,13 @@ int simrank_shardplan_info(const simrank_shardplan* p, int64_t* n, int64_t* col_
 int simrank_shardplan_get(const simrank_shardplan* p, const char* key, int64_t* value) {
     SR_REQUIRE(p && key && value, "NULL argument");
     if (!strcmp(key, "restrict_support")) *value = p->restrict_support;
+    else if (!strcmp(key, "iterate")) *value = (int64_t)(uintptr_t)p->S[p->cur];
+    else if (!strcmp(key, "iterate_layout")) *value = p->half ? 2 : 1;
+    else if (!strcmp(key, "iterate_stride")) *value = p->half ? p->rows_pad : p->ld;
+    else if (!strcmp(key, "iterate_rows")) *value = p->n;
+    else if (!strcmp(key, "iterate_col_lo")) *value = p->m_lo;
+    else if (!strcmp(key, "iterate_col_hi")) *value = p->m_hi;
+    else if (!strcmp(key, "ids")) *value = (int64_t)(uintptr_t)p->ord_dev;
     else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }

@@ -126,6 +126,111 @@ def _progress_callback(on_iteration, on_converged):
     return _lib.PROGRESS_FN(hook), raised
 
 
+# ---- pairs above a threshold: libsimrank_select.so (include/simrank_select.h) on a plan's iterate, in place ----
+def _iterate_block(get) -> dict:
+    """What a reader of a plan's CURRENT iterate needs, through its getter (simrank_plan_get & co, include/simrank_hip.h)."""
+    ptr = get("iterate")
+    if not ptr:
+        raise ValueError("the plan's matrices were released: select pairs before release() / trim()")
+    ids, lo = get("ids"), get("iterate_col_lo")
+    return dict(ptr=ptr, layout=get("iterate_layout"), stride=get("iterate_stride"), rows=get("iterate_rows"),
+                cols=get("iterate_col_hi") - lo, row_ids=ids, col_ids=ids + 4 * lo)
+
+
+class Selection:
+    """The two passes of libsimrank_select.so over blocks of one iterate that share their rows (a plan's matrix, or the
+    column blocks of this process's ranks) on ``ops``' stream.  Constructing it runs the COUNT pass and scans the counts
+    (``total``: pairs in all blocks; nothing else crosses PCIe); ``emit()`` runs the EMIT pass and brings the hits back
+    per block, rows in the solver's order; ``pairs()`` puts them into the caller's order.  ``timing``: HIP events around
+    each pass (``count_ms`` / ``emit_ms``, summed over the blocks)."""
+
+    def __init__(self, ops, blocks, t, timing: bool = False):
+        from . import _select
+        self.ops, self.blocks, self.timing = ops, blocks, timing
+        self.sel = _select.load()
+        self.t32 = _select.threshold_f32(t)
+        self.n = n = blocks[0]["rows"]
+        self.count_ms = self.emit_ms = 0.0
+        assert all(b["rows"] == n for b in blocks)
+        lib = ops.lib
+        self.offsets = []
+        cnt_dev = ops._malloc(4 * n)
+        counts = np.empty(n, dtype=np.int32)
+        try:
+            for b in blocks:
+                self._timed("count_ms", lambda: _select.check(self.sel.simrank_select_count(
+                    b["ptr"], b["layout"], b["stride"], n, b["cols"], b["row_ids"], b["col_ids"], self.t32, cnt_dev,
+                    ops.stream), "simrank_select_count"))
+                check(lib.simrank_memcpy_d2h(counts.ctypes.data, C.c_void_p(cnt_dev), 4 * n, ops.stream), "simrank_memcpy_d2h")
+                check(lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+                off = np.empty(n + 1, dtype=np.int64)
+                _select.check(self.sel.simrank_select_offsets(counts.ctypes.data, n, off.ctypes.data, None),
+                              "simrank_select_offsets")
+                self.offsets.append(off)
+            # the rows' caller ids (the same for every block: one solver order)
+            self.row_order = np.empty(n, dtype=np.int32)
+            check(lib.simrank_memcpy_d2h(self.row_order.ctypes.data, C.c_void_p(blocks[0]["row_ids"]), 4 * n, ops.stream),
+                  "simrank_memcpy_d2h")
+            check(lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+        finally:
+            ops._free(cnt_dev)
+        self.total = sum(int(o[-1]) for o in self.offsets)
+
+    def _timed(self, key, launch):
+        if not self.timing:
+            launch()
+            return
+        a, b = self.ops.event(), self.ops.event()
+        try:
+            self.ops.record(a)
+            launch()
+            self.ops.record(b)
+            self.ops.event_synchronize(b)
+            setattr(self, key, getattr(self, key) + self.ops.elapsed_ms(a, b))
+        finally:
+            self.ops.event_destroy(a)
+            self.ops.event_destroy(b)
+
+    def emit(self):
+        """[(offsets int64 [n + 1], caller ids int32, values float32)] per block, rows in the solver's order."""
+        from . import _select
+        ops, lib, n = self.ops, self.ops.lib, self.n
+        pieces = []
+        for b, off in zip(self.blocks, self.offsets):
+            tot = int(off[-1])
+            ids = np.empty(tot, dtype=np.int32)
+            vals = np.empty(tot, dtype=np.float32)
+            if tot:
+                bufs = [ops._malloc(8 * (n + 1)), ops._malloc(4 * tot), ops._malloc(4 * tot)]
+                try:
+                    off_dev, ids_dev, val_dev = bufs
+                    check(lib.simrank_memcpy_h2d(C.c_void_p(off_dev), off.ctypes.data, 8 * (n + 1), ops.stream),
+                          "simrank_memcpy_h2d")
+                    self._timed("emit_ms", lambda: _select.check(self.sel.simrank_select_emit(
+                        b["ptr"], b["layout"], b["stride"], n, b["cols"], b["row_ids"], b["col_ids"], self.t32, off_dev,
+                        tot, ids_dev, val_dev, ops.stream), "simrank_select_emit"))
+                    check(lib.simrank_memcpy_d2h(ids.ctypes.data, C.c_void_p(ids_dev), 4 * tot, ops.stream), "simrank_memcpy_d2h")
+                    check(lib.simrank_memcpy_d2h(vals.ctypes.data, C.c_void_p(val_dev), 4 * tot, ops.stream), "simrank_memcpy_d2h")
+                    check(lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+                finally:
+                    for ptr in bufs:
+                        ops._free(ptr)
+            pieces.append((off, ids, vals))
+        return pieces
+
+    def pairs(self):
+        """(offsets int64 [n + 1] by caller row, neighbour ids int32, values float32), each row's ids ascending."""
+        from . import _select
+        return _select.merge(self.emit(), self.row_order)
+
+
+def _pairs_above(sel: Selection, max_pairs):
+    from . import _select
+    if max_pairs is not None and sel.total > max_pairs:
+        raise _select.too_many(sel.total, max_pairs)
+    return sel.pairs()
+
+
 class Plan:
     """The reference loop on one GPU behind the C ABI (simrank_plan_*: SimRank.py:124-141, :346-363,
     :440-455): CSR + per-row scale in the caller's node order in, S (float64, caller's order) out."""
@@ -226,6 +331,16 @@ class Plan:
         check(self.ops.lib.simrank_plan_topk(self.handle, int(k), int(exclude_diag), idx.ctypes.data, val.ctypes.data),
               "simrank_plan_topk")
         return idx, val
+
+    def selection(self, t, timing: bool = False) -> Selection:
+        """The count pass of ``pairs_above`` (``Selection``): the current iterate, read in place."""
+        return Selection(self.ops, [_iterate_block(self.get)], t, timing)
+
+    def pairs_above(self, t, max_pairs=2 ** 27):
+        """(offsets int64 [n + 1], neighbour ids int32, values float32): row i (caller's order) lists the OTHER nodes c
+        with float64(S[i][c]) >= t, ascending — the masked ``np.nonzero`` of the dense result.  ValueError, with nothing
+        transferred, when more than ``max_pairs`` pairs qualify.  Before ``trim``."""
+        return _pairs_above(self.selection(t), max_pairs)
 
     def free(self):
         if self.handle:
@@ -367,6 +482,18 @@ class ShardPlans:
                                                   idx.ctypes.data if i_am_root else None,
                                                   val.ctypes.data if i_am_root else None), "simrank_shardplan_topk")
         return idx, val
+
+    def selection(self, t, timing: bool = False) -> Selection:
+        """The count pass over the column blocks of this process's plans (every rank of an in-process group; this rank's
+        block in an RCCL world)."""
+        lib = self.ops.lib
+        return Selection(self.ops, [_iterate_block(lambda k, h=h: _shardplan_get(lib, h, k)) for h in self.plans], t,
+                         timing)
+
+    def pairs_above(self, t, max_pairs=2 ** 27):
+        """As ``Plan.pairs_above``, over the column blocks of this process's plans (the whole matrix in an in-process
+        group): the blocks' hits concatenated per row, then sorted."""
+        return _pairs_above(self.selection(t), max_pairs)
 
     def free(self):
         lib = self.ops.lib
@@ -518,6 +645,15 @@ class ShardBiPlans:
                                                   val.ctypes.data if i_am_root else None), "simrank_shardplan_topk")
         return idx, val
 
+    def selection(self, group: int, t, timing: bool = False) -> Selection:
+        lib = self.ops.lib
+        return Selection(self.ops, [_iterate_block(lambda k, h=h: _shardplan_get(lib, C.c_void_p(h), k))
+                                    for h in self._sides[group]], t, timing)
+
+    def pairs_above(self, group: int, t, max_pairs=2 ** 27):
+        """As ``ShardPlans.pairs_above``, for group 1 | 2."""
+        return _pairs_above(self.selection(group, t), max_pairs)
+
     def free(self):
         lib = self.ops.lib
         for h in self.pairs:
@@ -611,6 +747,13 @@ class BiPlan:
         v = C.c_int64(0)
         check(self.ops.lib.simrank_biplan_get(self.handle, int(group), key.encode(), C.byref(v)), f"simrank_biplan_get({key})")
         return v.value
+
+    def selection(self, group: int, t, timing: bool = False) -> Selection:
+        return Selection(self.ops, [_iterate_block(lambda k: self.get(group, k))], t, timing)
+
+    def pairs_above(self, group: int, t, max_pairs=2 ** 27):
+        """As ``Plan.pairs_above``, for group 1 | 2."""
+        return _pairs_above(self.selection(group, t), max_pairs)
 
     def evidence_counts(self, group: int) -> np.ndarray:
         """uint8 [n, n] counts gating group 1 | 2's update, caller's order."""

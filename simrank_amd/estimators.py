@@ -18,6 +18,14 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
     top_k             return, instead of the dense matrix, a long-format frame (node, rank,
                       neighbor, similarity) with the k most similar other nodes of every node,
                       selected on the device (no N x N transfer)
+    min_similarity    return, instead of the dense matrix, a long-format frame (node, neighbor, similarity) with
+                      every pair of DIFFERENT nodes whose similarity is >= min_similarity (float64 comparison of
+                      the stored value; rows grouped by node in the dense frame's label order, neighbours
+                      ascending in it: the dense frame's masked ``np.nonzero``), selected on the device
+                      (libsimrank_select.so; no N x N transfer).  With top_k: the top-k frame without its rows
+                      below the threshold
+    max_pairs         (with min_similarity) refuse with ValueError, before anything is transferred, when more
+                      pairs than this qualify (default 2**27)
     dense_precision   "f32" (default) | "fp16": operand precision of the matrix-core part of the legs;
                       "fp16" is BASELINE.json config 5's reduced-precision dense leg, outside the parity bar
     strict_reference  bipartite classes only; True keeps quirks Q1 (set-order labels on
@@ -191,6 +199,43 @@ def _topk_frame(solver, j, k, labels):
         "similarity": val.ravel()[keep]})
 
 
+def _check_pairs_args(min_similarity, max_pairs):
+    """``min_similarity`` / ``max_pairs`` checked before any device work (ValueError)."""
+    if min_similarity is not None:
+        from ._select import check_threshold
+        check_threshold(min_similarity, max_pairs)
+
+
+def _pairs_frame(solver, j, t, max_pairs, labels):
+    """Long-format hand-back: one row per (node, neighbor) pair of different nodes with similarity >= t."""
+    if not hasattr(solver, "pairs"):
+        raise ValueError("min_similarity needs a solver behind the C ABI (fit on one GPU, LocalWorld(P) or an RCCL "
+                         "TorchWorld)")
+    got = solver.pairs(j, t, max_pairs)
+    if got is None:                       # multi-process world, root-only hand-back: not the root
+        return None
+    offsets, ids, vals = got
+    lab = pd.Index(labels)
+    return pd.DataFrame({
+        "node": lab.take(np.repeat(np.arange(len(lab)), np.diff(offsets))),
+        "neighbor": lab.take(ids.astype(np.intp)),
+        "similarity": vals.astype(np.float64)})
+
+
+def _result_frames(solver, sides, top_k, min_similarity, max_pairs):
+    """The long-format hand-backs of ``fit(top_k=..., min_similarity=...)``, one per (side j, labels); releases the
+    solver's matrices."""
+    try:
+        if top_k:
+            out = [_topk_frame(solver, j, top_k, lab) for j, lab in sides]
+            if min_similarity is not None:
+                out = [f[f["similarity"].to_numpy() >= float(min_similarity)].reset_index(drop=True) for f in out]
+            return out
+        return [_pairs_frame(solver, j, min_similarity, max_pairs, lab) for j, lab in sides]
+    finally:
+        solver.release()
+
+
 def _is_symmetric(prior) -> bool:
     """The fused two-gather update needs symmetric iterates; everything the reference builds
     is symmetric except what a user-supplied prior (SimRank.py:453) brings in."""
@@ -225,9 +270,11 @@ class SimRank(object):
     def _side(self, csr, C):
         return SideSpec(csr, csr.rowscale, C)
 
-    def _finish(self, solver, k, top_k=None):
+    def _finish(self, solver, k, top_k=None, min_similarity=None, max_pairs=2 ** 27):
         self.converged_at = k
         self.engine_mode = solver.mode
+        if min_similarity is not None:
+            return _result_frames(solver, [(0, self._order)], top_k, min_similarity, max_pairs)[0]
         if top_k:
             out = _topk_frame(solver, 0, top_k, self._order)
             solver.release()
@@ -240,13 +287,14 @@ class SimRank(object):
 
     def fit(self, data, C=0.8, weighted=False, from_node_column="from", to_node_column="to",
             weight_column="weight", iterations=100, eps=1e-4, verbose=True, *,
-            mode="auto", device=None, world=None, top_k=None, dense_precision="f32", storage_precision="f32",
-            _ops_factory=None):
+            mode="auto", device=None, world=None, top_k=None, min_similarity=None, max_pairs=2 ** 27,
+            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+        _check_pairs_args(min_similarity, max_pairs)
         with _precision(dense_precision, storage_precision):
             csr = self._create_graph(data, weighted, from_node_column, to_node_column, weight_column)
             solver, k = _solve([self._side(csr, C)], iterations, eps, verbose, mode, device, world,
                                _ops_factory)
-            return self._finish(solver, k, top_k)
+            return self._finish(solver, k, top_k, min_similarity, max_pairs)
 
 
 class SimRankPP(SimRank):
@@ -276,7 +324,7 @@ class SimRankPP(SimRank):
 
     def _fit_pp(self, data, C, weighted, from_node_column, to_node_column, weight_column,
                 iterations, eps, verbose, mode, device, world, ops_factory, apriori=None,
-                lbd=0.0, top_k=None):
+                lbd=0.0, top_k=None, min_similarity=None, max_pairs=2 ** 27):
         csr = self._create_graph(data, weighted, from_node_column, to_node_column, weight_column)
         talk = verbose and (world is None or world.is_root)
         spec = self._pp_side(csr, C, talk, apriori, lbd)
@@ -296,16 +344,17 @@ class SimRankPP(SimRank):
                        on_iteration=(lambda i: update_progress(i / iterations)) if talk else None,
                        on_converged=announce_converged if talk else None)
         self.Evidence = _lazy_evidence(world, solver, 0, csr)
-        return self._finish(solver, k, top_k)
+        return self._finish(solver, k, top_k, min_similarity, max_pairs)
 
     def fit(self, data, C=0.8, weighted=False, from_node_column="from", to_node_column="to",
             weight_column="weight", iterations=100, eps=1e-4, verbose=True, *,
-            mode="auto", device=None, world=None, top_k=None, dense_precision="f32", storage_precision="f32",
-            _ops_factory=None):
+            mode="auto", device=None, world=None, top_k=None, min_similarity=None, max_pairs=2 ** 27,
+            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+        _check_pairs_args(min_similarity, max_pairs)
         with _precision(dense_precision, storage_precision):
             return self._fit_pp(data, C, weighted, from_node_column, to_node_column, weight_column,
                                 iterations, eps, verbose, mode, device, world, _ops_factory,
-                                top_k=top_k)
+                                top_k=top_k, min_similarity=min_similarity, max_pairs=max_pairs)
 
 
 class AprioriSimRank(SimRankPP):
@@ -316,15 +365,17 @@ class AprioriSimRank(SimRankPP):
 
     def fit(self, data, AprioriSim, C=0.8, lbd=0.5, weighted=False, from_node_column="from",
             to_node_column="to", weight_column="weight", iterations=100, eps=1e-4,
-            verbose=True, *, mode="auto", device=None, world=None, top_k=None,
-            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            verbose=True, *, mode="auto", device=None, world=None, top_k=None, min_similarity=None,
+            max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32", _ops_factory=None):
+        _check_pairs_args(min_similarity, max_pairs)
         with _precision(dense_precision, storage_precision):
             if not isinstance(AprioriSim, np.ndarray):
                 # the reference fails at np.fill_diagonal for anything but an ndarray
                 raise AttributeError(f"'{type(AprioriSim).__name__}' object has no attribute 'flat'")
             return self._fit_pp(data, C, weighted, from_node_column, to_node_column, weight_column,
                                 iterations, eps, verbose, mode, device, world, _ops_factory,
-                                apriori=AprioriSim, lbd=lbd, top_k=top_k)
+                                apriori=AprioriSim, lbd=lbd, top_k=top_k, min_similarity=min_similarity,
+                                max_pairs=max_pairs)
 
 
 # ----------------------------------------------------------------------------------------
@@ -354,10 +405,13 @@ class BipartiteSimRank(object):
         self.Graph_N2_N1 = lambda: pd.DataFrame(g21.dense(), index=lab2, columns=lab1)
         return g12, g21
 
-    def _finish(self, solver, k, strict_reference, top_k=None):
+    def _finish(self, solver, k, strict_reference, top_k=None, min_similarity=None, max_pairs=2 ** 27):
         self.converged_at = k
         self.engine_mode = solver.mode
         l1, l2 = self._set_order if strict_reference else map(list, self._sorted)
+        if min_similarity is not None:
+            out = _result_frames(solver, [(0, l1), (1, l2)], top_k, min_similarity, max_pairs)
+            return None if out[0] is None else tuple(out)
         if top_k:
             out = (_topk_frame(solver, 0, top_k, l1), _topk_frame(solver, 1, top_k, l2))
             solver.release()
@@ -371,13 +425,15 @@ class BipartiteSimRank(object):
     def fit(self, data, C1=0.8, C2=0.8, weighted=False, node_group1_column="user",
             node_group2_column="item", weight_column="weight", iterations=100, eps=1e-4,
             verbose=True, *, mode="auto", device=None, world=None, strict_reference=True,
-            top_k=None, dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            top_k=None, min_similarity=None, max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32",
+            _ops_factory=None):
+        _check_pairs_args(min_similarity, max_pairs)
         with _precision(dense_precision, storage_precision):
             g12, g21 = self._create_graph(data, weighted, node_group1_column, node_group2_column,
                                           weight_column)
             specs = [SideSpec(g12, g12.rowscale, C1), SideSpec(g21, g21.rowscale, C2)]
             solver, k = _solve(specs, iterations, eps, verbose, mode, device, world, _ops_factory)
-            return self._finish(solver, k, strict_reference, top_k)
+            return self._finish(solver, k, strict_reference, top_k, min_similarity, max_pairs)
 
 
 class BipartiteSimRankPP(SimRankPP):
@@ -401,7 +457,8 @@ class BipartiteSimRankPP(SimRankPP):
 
     def _fit_bpp(self, data, C1, C2, weighted, node_group1_column, node_group2_column,
                  weight_column, iterations, eps, verbose, mode, device, world, strict_reference,
-                 ops_factory, priors=(None, None), lbds=(0.0, 0.0), top_k=None):
+                 ops_factory, priors=(None, None), lbds=(0.0, 0.0), top_k=None, min_similarity=None,
+                 max_pairs=2 ** 27):
         g12, g21 = self._create_graph(data, weighted, node_group1_column, node_group2_column,
                                       weight_column)
         world = world or LocalWorld(1)
@@ -435,16 +492,19 @@ class BipartiteSimRankPP(SimRankPP):
         self.Evidence_N1 = _lazy_evidence(world, solver, 0, g12)
         self.Evidence_N2 = ((lambda: _host_evidence(g21)) if strict_reference
                             else _lazy_evidence(world, solver, 1, g21))
-        return self._finish(solver, k, strict_reference, top_k)
+        return self._finish(solver, k, strict_reference, top_k, min_similarity, max_pairs)
 
     def fit(self, data, C1=0.8, C2=0.8, weighted=False, node_group1_column="user",
             node_group2_column="item", weight_column="weight", iterations=100, eps=1e-4,
             verbose=True, *, mode="auto", device=None, world=None, strict_reference=True,
-            top_k=None, dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            top_k=None, min_similarity=None, max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32",
+            _ops_factory=None):
+        _check_pairs_args(min_similarity, max_pairs)
         with _precision(dense_precision, storage_precision):
             return self._fit_bpp(data, C1, C2, weighted, node_group1_column, node_group2_column,
                                  weight_column, iterations, eps, verbose, mode, device, world,
-                                 strict_reference, _ops_factory, top_k=top_k)
+                                 strict_reference, _ops_factory, top_k=top_k, min_similarity=min_similarity,
+                                 max_pairs=max_pairs)
 
 
 class BipartitleAprioriSimRank(BipartiteSimRankPP):
@@ -457,8 +517,9 @@ class BipartitleAprioriSimRank(BipartiteSimRankPP):
     def fit(self, data, AprioriSim1, AprioriSim2, C1=0.8, C2=0.8, lbd1=0.5, lbd2=0.5,
             weighted=False, node_group1_column="user", node_group2_column="item",
             weight_column="weight", iterations=100, eps=1e-4, verbose=True, *, mode="auto",
-            device=None, world=None, strict_reference=True, top_k=None, dense_precision="f32", storage_precision="f32",
-            _ops_factory=None):
+            device=None, world=None, strict_reference=True, top_k=None, min_similarity=None, max_pairs=2 ** 27,
+            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+        _check_pairs_args(min_similarity, max_pairs)
         with _precision(dense_precision, storage_precision):
             for a in (AprioriSim1, AprioriSim2):
                 if not isinstance(a, np.ndarray):
@@ -466,7 +527,8 @@ class BipartitleAprioriSimRank(BipartiteSimRankPP):
             return self._fit_bpp(data, C1, C2, weighted, node_group1_column, node_group2_column,
                                  weight_column, iterations, eps, verbose, mode, device, world,
                                  strict_reference, _ops_factory, priors=(AprioriSim1, AprioriSim2),
-                                 lbds=(lbd1, lbd2), top_k=top_k)
+                                 lbds=(lbd1, lbd2), top_k=top_k, min_similarity=min_similarity,
+                                 max_pairs=max_pairs)
 
 
 def _lazy_evidence(world, solver, j, csr):
