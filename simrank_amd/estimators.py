@@ -28,6 +28,8 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
                       pairs than this qualify (default 2**27)
     dense_precision   "f32" (default) | "fp16": operand precision of the matrix-core part of the legs;
                       "fp16" is BASELINE.json config 5's reduced-precision dense leg, outside the parity bar
+    storage_precision "f32" (default) | "fp16" (config 5's matrices held in fp16, outside the parity bar) | "f64"
+                      (the reference's float64 loop on one GPU: libsimrank_f64.so; every hand-back float64)
     strict_reference  bipartite classes only; True keeps quirks Q1 (set-order labels on
                       sorted-order data) and Q2 (Evidence_N1 on the group-2 update, a
                       ValueError when n1 != n2); False labels correctly and uses Evidence_N2
@@ -62,15 +64,18 @@ def _precision(dense_precision, storage_precision="f32"):
     mode, symmetric iterates; one GPU — or, for SimRank / SimRank++ without a prior, the ranks of a
     ``LocalWorld(P)`` / RCCL ``TorchWorld``: ``cshard.py``, the sharded loop behind the C ABI) — half the
     bytes and half the gathered lines per update (and half the bytes on the links), the
-    reduced-precision mode that pays on config 5; NOT within the parity bar either.  In that mode the
+    reduced-precision mode that pays on config 5; NOT within the parity bar either.  Or "f64": the reference's own
+    precision — every matrix, product, prior and convergence test in float64 on one GPU (``cdouble.py``,
+    libsimrank_f64.so), for a tight ``eps`` or the reference's exact numbers; exact products only (dense_precision
+    "f32"), no sharded worlds.  In the fp16 mode the
     convergence test is NOT the reference's `_converged` (SimRank.py:54-77): an element counts as moved only
     when it moved by more than eps + half an fp16 spacing at its stored value, so ``converged_at`` and the
     number of updates are not comparable with the reference's (the loop usually ends one or two updates
     later on SimRank++ matrices, much later on matrices full of values above 1/8)."""
     if dense_precision not in _DENSE_TERMS:
         raise ValueError(f"dense_precision must be one of {sorted(_DENSE_TERMS)}, not {dense_precision!r}")
-    if storage_precision not in ("f32", "fp16"):
-        raise ValueError(f"storage_precision must be 'f32' or 'fp16', not {storage_precision!r}")
+    if storage_precision not in ("f32", "fp16", "f64"):
+        raise ValueError(f"storage_precision must be 'f32', 'fp16' or 'f64', not {storage_precision!r}")
     stack = _precision_now.__dict__.setdefault("stack", [("f32", "f32")])
     stack.append((dense_precision, storage_precision))
     try:
@@ -98,6 +103,14 @@ def _make_solver(ops_factory, device, world, specs, mode):
     terms = _DENSE_TERMS[dense]
     if terms != 3 or storage != "f32":
         specs = [dataclasses.replace(s, dense_terms=terms, storage=storage) for s in specs]
+    if storage == "f64":
+        # the reference's float64 loop (cdouble.py, libsimrank_f64.so): one GPU; what it does not run is refused here,
+        # before any device work
+        from . import cdouble
+        why = cdouble.refusal(world, specs, mode, ops_factory)
+        if why is not None:
+            raise ValueError(why)
+        return cdouble.F64Solver(_default_ops_factory(device)(0), world, specs)
     if mode not in ("auto", "sparse", "dense", "hybrid"):
         raise ValueError(f"mode must be 'auto' or 'sparse', not {mode!r}")
     loop = getattr(world, "loop", "c")
