@@ -113,6 +113,11 @@ SIMRANK_F64_API int simrank_f64_plan_emit_above(simrank_f64_plan* p, int32_t sid
                                                 int32_t* ids_host, double* vals_host);
 /* Release the matrices (result, topk and the selection fail afterwards). */
 SIMRANK_F64_API int simrank_f64_plan_trim(simrank_f64_plan* p);
+/* Where side `side`'s CURRENT matrix is, for a reader that works on it in place (include/simrank_query.h, layout
+ * float64 row-major): "iterate" the device address (0 after simrank_f64_plan_trim; it moves with every step, so ask
+ * after the loop), "iterate_ld" its pitch in doubles, "iterate_rows" n.  Rows and columns are in the caller's order.
+ * SIMRANK_F64_ERR_INVALID for a NULL argument, a side out of range or an unknown key. */
+SIMRANK_F64_API int simrank_f64_plan_get(const simrank_f64_plan* p, int32_t side, const char* key, int64_t* value);
 
 #ifdef __cplusplus
 }

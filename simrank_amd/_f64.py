@@ -45,6 +45,7 @@ PROTOTYPES = {
     "simrank_f64_plan_count_above": [_vp, _i32, _f64, _vp],
     "simrank_f64_plan_emit_above": [_vp, _i32, _f64, _i64, _vp, _vp],
     "simrank_f64_plan_trim": [_vp],
+    "simrank_f64_plan_get": [_vp, _i32, C.c_char_p, C.POINTER(_i64)],
 }
 _RESTYPES = {"simrank_f64_last_error": C.c_char_p}
 

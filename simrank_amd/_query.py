@@ -1,0 +1,320 @@
+"""ctypes binding of libsimrank_query.so (include/simrank_query.h): node queries on a model that stays on the device.
+
+A companion of libsimrank_hip.so with its own header, version and binding, so that the main library's C ABI stays as it
+is; it reads the iterate a plan reports through ``simrank_plan_get`` & co in place.  ``Reader`` runs the three queries over
+the column blocks of one kept iterate (one block on one GPU, one per virtual rank of a ``LocalWorld(P)``).  No CPU
+fallback: a missing library or device is an error.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import numbers
+import os
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libsimrank_query.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simrank_query.h")
+
+VERSION = 1              # SIMRANK_QUERY_VERSION of include/simrank_query.h
+PANEL_F32, ROWMAJOR_F32, PANEL_F16, ROWMAJOR_F64 = 0, 1, 2, 3
+
+SLAB_BYTES = 256 << 20   # device block of one band of ``rows`` (a larger request is cut into bands of query rows)
+
+_vp, _i64, _i32 = C.c_void_p, C.c_int64, C.c_int32
+
+# name -> argtypes (restype is int unless listed in _RESTYPES)
+PROTOTYPES = {
+    "simrank_query_version": [],
+    "simrank_query_last_error": [],
+    "simrank_query_rows": [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
+    "simrank_query_pairs": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp],
+    "simrank_query_topk": [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp],
+    "simrank_query_merge_topk": [_i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp],
+}
+_RESTYPES = {"simrank_query_last_error": C.c_char_p}
+
+
+class QueryError(RuntimeError):
+    """A call into libsimrank_query.so failed."""
+
+
+_lib = None
+
+
+def load():
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise QueryError(f"{LIB_PATH} is missing: build it with `make -C simrank_amd/csrc` (no CPU fallback)")
+        lib = C.CDLL(LIB_PATH)
+        for name, argtypes in PROTOTYPES.items():
+            fn = getattr(lib, name)
+            fn.argtypes = argtypes
+            fn.restype = _RESTYPES.get(name, C.c_int)
+        if lib.simrank_query_version() != VERSION:
+            raise QueryError(f"libsimrank_query.so version {lib.simrank_query_version()} != {VERSION}")
+        _lib = lib
+    return _lib
+
+
+def check(rc: int, what: str):
+    if rc != 0:
+        msg = load().simrank_query_last_error().decode(errors="replace")
+        raise QueryError(f"{what} failed ({rc}): {msg}")
+
+
+def check_k(k):
+    """``most_similar(nodes, k)`` / ``top_k(k)``: k a positive integer (ValueError otherwise; nothing touches a device)."""
+    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or int(k) < 1:
+        raise ValueError(f"k must be a positive integer, not {k!r}")
+    return int(k)
+
+
+def merge_topk(pieces, k: int):
+    """Host: pieces [(ids int32 [n_q, k_p], values float64 [n_q, k_p])] over the same query rows, one per column block
+    (id -1 = empty slot) -> (ids int32 [n_q, k], values float64 [n_q, k]): each row's k best in the order (value
+    descending, id ascending), empty slots as id -1 / value 0."""
+    import numpy as np
+    pieces = [(np.ascontiguousarray(i, dtype=np.int32), np.ascontiguousarray(v, dtype=np.float64)) for i, v in pieces]
+    n_q = pieces[0][0].shape[0] if pieces else 0
+    k = check_k(k)
+    for i, v in pieces:
+        if i.ndim != 2 or i.shape != v.shape or i.shape[0] != n_q:
+            raise ValueError("every piece is (ids [n_q, k_p], values [n_q, k_p]) over the same n_q rows")
+    idx = np.empty((n_q, k), dtype=np.int32)
+    val = np.empty((n_q, k), dtype=np.float64)
+    P = len(pieces)
+    ids = (C.c_void_p * max(1, P))(*[i.ctypes.data if i.size else None for i, _ in pieces])
+    vals = (C.c_void_p * max(1, P))(*[v.ctypes.data if v.size else None for _, v in pieces])
+    ks = (C.c_int32 * max(1, P))(*[i.shape[1] for i, _ in pieces])
+    check(load().simrank_query_merge_topk(P, ids, vals, ks, n_q, k, idx.ctypes.data if n_q else None,
+                                          val.ctypes.data if n_q else None), "simrank_query_merge_topk")
+    return idx, val
+
+
+class SolverQueries:
+    """What a kept solver (``cplan.PlanSolver``, ``cshard.CShardSolver``, ``cdouble.F64Solver``) answers node queries
+    with: one ``Reader`` per side, made on first use by the solver's ``_make_reader(j)`` and closed at ``release``."""
+
+    _readers = None
+
+    def _reader(self, j):
+        if self._readers is None:
+            self._readers = {}
+        if j not in self._readers:
+            self._readers[j] = self._make_reader(j)
+        return self._readers[j]
+
+    def rows(self, j, node_ids):
+        """float64 [len(node_ids), n]: side j's rows of those nodes (caller's ids), columns in the caller's order."""
+        return self._reader(j).rows(node_ids)
+
+    def pair_values(self, j, a_ids, b_ids):
+        """float64 [len(a_ids)]: side j's S[a][b] per pair of node ids."""
+        return self._reader(j).pair_values(a_ids, b_ids)
+
+    def topk_of(self, j, node_ids, k):
+        """(ids int32 [len(node_ids), k], values float64): the k most similar OTHER nodes of those nodes, k clamped as
+        the solver's ``topk`` clamps it."""
+        k = int(min(k, max(1, self.n[j] - 1)))
+        return self._reader(j).topk_of(node_ids, k)
+
+    def _close_readers(self):
+        readers, self._readers = self._readers or {}, None
+        for r in readers.values():
+            r.close()
+
+
+class Reader:
+    """The queries of one kept iterate: ``blocks`` as ``engine._iterate_block`` describes them (dicts with ptr, layout,
+    stride, rows, cols, col_lo, col_ids), all over the same rows in the solver's order ``order`` (host int32: caller id of
+    position r), on ``ops``' stream.  Node ids in, values in the caller's order out; every call ends synchronised."""
+
+    def __init__(self, ops, blocks, order):
+        import numpy as np
+        self.ops, self.blocks = ops, blocks
+        self.q = load()
+        self.n = int(order.size)
+        self.order = np.ascontiguousarray(order, dtype=np.int32)
+        self.inv = np.empty(self.n, dtype=np.int32)           # caller id -> solver position
+        self.inv[self.order] = np.arange(self.n, dtype=np.int32)
+        self._maps = {}                                        # block index -> device int32 column map (made on first use)
+
+    # ---- device scratch ---------------------------------------------------------------------------------------------
+    def _upload_i32(self, host):
+        from .engine import check as hip_check
+        ptr = self.ops._malloc(max(4, 4 * host.size))
+        if host.size:
+            hip_check(self.ops.lib.simrank_memcpy_h2d(C.c_void_p(ptr), host.ctypes.data, 4 * host.size, self.ops.stream),
+                      "simrank_memcpy_h2d")
+        return ptr
+
+    def _d2h(self, host, ptr, nbytes):
+        from .engine import check as hip_check
+        hip_check(self.ops.lib.simrank_memcpy_d2h(host.ctypes.data, C.c_void_p(ptr), nbytes, self.ops.stream),
+                  "simrank_memcpy_d2h")
+
+    def _sync(self):
+        from .engine import check as hip_check
+        hip_check(self.ops.lib.simrank_stream_synchronize(self.ops.stream), "simrank_stream_synchronize")
+
+    def _col_map(self, i):
+        """Block i's columns in the caller's order: positions (within the block) sorted by caller id, on the device;
+        with them the caller ids they go to (host).  One block holding every column: the inverse of the order."""
+        import numpy as np
+        got = self._maps.get(i)
+        if got is None:
+            b = self.blocks[i]
+            ids = self.order[b["col_lo"]:b["col_lo"] + b["cols"]]
+            if np.array_equal(ids, np.arange(ids.size, dtype=np.int32)):
+                got = self._maps[i] = (None, ids)              # (the caller's order already: no map)
+            else:
+                pos = np.ascontiguousarray(np.argsort(ids, kind="stable").astype(np.int32))
+                got = self._maps[i] = (self._upload_i32(pos), np.ascontiguousarray(ids[pos]))
+                self._sync()
+        return got
+
+    def close(self):
+        for ptr, _ in self._maps.values():
+            if ptr is not None:
+                self.ops._free(ptr)
+        self._maps = {}
+
+    # ---- queries ----------------------------------------------------------------------------------------------------
+    def rows(self, node_ids, out=None, timing=None):
+        """float64 [len(node_ids), n]: those rows of the iterate, columns in the caller's order.  The device block of a
+        band holds at most ``SLAB_BYTES``; each band is one kernel per column block and one copy into ``out``.
+        ``timing``: a list that receives the kernels' milliseconds (HIP events; serialises the bands)."""
+        import numpy as np
+        from . import hostpool
+        ops, n = self.ops, self.n
+        node_ids = np.ascontiguousarray(node_ids, dtype=np.int32)
+        n_q = int(node_ids.size)
+        if out is None:
+            out = hostpool.empty_f64(n_q, n)
+        if n_q == 0 or n == 0:
+            return out
+        pos_dev = self._upload_i32(self.inv[node_ids])
+        whole = len(self.blocks) == 1
+        band = int(max(1, min(n_q, SLAB_BYTES // (8 * n))))
+        slab = ops._malloc(8 * band * n)
+        stage = None if whole else np.empty((band, n), dtype=np.float64)
+        try:
+            for q0 in range(0, n_q, band):
+                m = min(band, n_q - q0)
+                off = 0
+                for i, b in enumerate(self.blocks):
+                    cmap, _ = self._col_map(i)
+                    launch = lambda b=b, cmap=cmap, off=off: check(self.q.simrank_query_rows(
+                        b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev + 4 * q0, m, cmap, b["cols"],
+                        slab + 8 * off, b["cols"], ops.stream), "simrank_query_rows")
+                    if timing is None:
+                        launch()
+                    else:
+                        timing.append(_timed(ops, launch))
+                    off += m * b["cols"]
+                if whole:
+                    self._d2h(out[q0:q0 + m], slab, 8 * m * n)
+                else:
+                    # every block's [m, cols] piece follows the other in the slab; its columns go to their caller ids
+                    self._d2h(stage, slab, 8 * m * n)
+                    self._sync()
+                    flat, off = stage.reshape(-1), 0
+                    for i, b in enumerate(self.blocks):
+                        out[q0:q0 + m, self._col_map(i)[1]] = flat[off:off + m * b["cols"]].reshape(m, b["cols"])
+                        off += m * b["cols"]
+            self._sync()
+        finally:
+            ops._free(slab)
+            ops._free(pos_dev)
+        return out
+
+    def pair_values(self, a_ids, b_ids):
+        """float64 [len(a_ids)]: S[a][b] per pair of node ids."""
+        import numpy as np
+        ops = self.ops
+        a = self.inv[np.ascontiguousarray(a_ids, dtype=np.int32)]
+        bp = self.inv[np.ascontiguousarray(b_ids, dtype=np.int32)]
+        m = int(a.size)
+        out = np.empty(m, dtype=np.float64)
+        if m == 0:
+            return out
+        a_dev = self._upload_i32(a)
+        val_dev = ops._malloc(8 * m)
+        try:
+            for b in self.blocks:
+                lo = b["col_lo"]
+                mine = np.nonzero((bp >= lo) & (bp < lo + b["cols"]))[0]
+                if not mine.size:
+                    continue
+                if mine.size == m:
+                    rows_dev, got = a_dev, out
+                else:
+                    rows_dev, got = self._upload_i32(np.ascontiguousarray(a[mine])), np.empty(mine.size, dtype=np.float64)
+                cols_dev = self._upload_i32(np.ascontiguousarray(bp[mine] - lo))
+                try:
+                    check(self.q.simrank_query_pairs(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], rows_dev,
+                                                     cols_dev, mine.size, val_dev, ops.stream), "simrank_query_pairs")
+                    self._d2h(got, val_dev, 8 * mine.size)
+                    self._sync()
+                finally:
+                    ops._free(cols_dev)
+                    if rows_dev != a_dev:
+                        ops._free(rows_dev)
+                if got is not out:
+                    out[mine] = got
+        finally:
+            ops._free(val_dev)
+            ops._free(a_dev)
+        return out
+
+    def topk_of(self, node_ids, k):
+        """(ids int32 [len(node_ids), k], values float64): the k most similar OTHER nodes of each node, caller's ids, in
+        the order (value descending, id ascending); id -1 / value 0 past the candidates.  Several column blocks: each
+        block's min(k, columns) candidates, merged on the host."""
+        import numpy as np
+        ops = self.ops
+        node_ids = np.ascontiguousarray(node_ids, dtype=np.int32)
+        n_q, k = int(node_ids.size), check_k(k)
+        if n_q == 0:
+            return np.empty((0, k), dtype=np.int32), np.empty((0, k), dtype=np.float64)
+        pos_dev = self._upload_i32(self.inv[node_ids])
+        ids_dev = self._upload_i32(node_ids)
+        pieces = []
+        try:
+            for b in self.blocks:
+                kk = int(min(k, b["cols"]))
+                if kk < 1:
+                    continue
+                idx, val = np.empty((n_q, kk), dtype=np.int32), np.empty((n_q, kk), dtype=np.float64)
+                idx_dev, val_dev = ops._malloc(4 * n_q * kk), ops._malloc(8 * n_q * kk)
+                try:
+                    check(self.q.simrank_query_topk(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev,
+                                                    ids_dev, n_q, b["col_ids"], kk, idx_dev, val_dev, ops.stream),
+                          "simrank_query_topk")
+                    self._d2h(idx, idx_dev, 4 * n_q * kk)
+                    self._d2h(val, val_dev, 8 * n_q * kk)
+                    self._sync()
+                finally:
+                    ops._free(idx_dev)
+                    ops._free(val_dev)
+                pieces.append((idx, val))
+        finally:
+            ops._free(ids_dev)
+            ops._free(pos_dev)
+        if len(pieces) == 1 and pieces[0][0].shape[1] == k:
+            return pieces[0]
+        return merge_topk(pieces, k)
+
+
+def _timed(ops, launch) -> float:
+    a, b = ops.event(), ops.event()
+    try:
+        ops.record(a)
+        launch()
+        ops.record(b)
+        ops.event_synchronize(b)
+        return ops.elapsed_ms(a, b)
+    finally:
+        ops.event_destroy(a)
+        ops.event_destroy(b)

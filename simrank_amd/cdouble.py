@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import _f64, hostpool
+from ._query import SolverQueries
 from ._f64 import F64MemoryError, check
 
 
@@ -134,6 +135,12 @@ class F64Plan:
                                                    vals.ctypes.data if total else None), "simrank_f64_plan_emit_above")
         return off, ids, vals
 
+    def get(self, side: int, key: str) -> int:
+        """Where side ``side``'s current matrix is (simrank_f64_plan_get): "iterate", "iterate_ld", "iterate_rows"."""
+        v = C.c_int64(0)
+        check(self.lib.simrank_f64_plan_get(self.handle, int(side), key.encode(), C.byref(v)), f"simrank_f64_plan_get({key})")
+        return v.value
+
     def trim(self):
         if self.handle:
             check(self.lib.simrank_f64_plan_trim(self.handle), "simrank_f64_plan_trim")
@@ -150,7 +157,7 @@ class F64Plan:
             pass
 
 
-class F64Solver:
+class F64Solver(SolverQueries):
     """``cplan.PlanSolver``'s surface over an ``F64Plan``."""
 
     mode = "sparse"
@@ -263,6 +270,19 @@ class F64Solver:
         cnt = self.ops[0].download(self._counts[id(csr)][1])
         return 1 - 0.5 ** cnt.astype(np.float64)
 
+    def _make_reader(self, j):
+        """Node queries on a kept model (``_query.SolverQueries``): side j's matrix as libsimrank_query.so's float64
+        row-major layout, rows and columns already in the caller's order (identity maps)."""
+        from . import _query
+        ptr = self.plan.get(j, "iterate")
+        if not ptr:
+            raise ValueError("the plan's matrices were released: query before release()")
+        n = self.plan.get(j, "iterate_rows")
+        block = dict(ptr=ptr, layout=_query.ROWMAJOR_F64, stride=self.plan.get(j, "iterate_ld"), rows=n, cols=n, col_lo=0,
+                     col_ids=None)
+        return _query.Reader(self.ops[0], [block], np.arange(n, dtype=np.int32))
+
     def release(self):
         """Free the matrices of the loop; the evidence counts stay (the ``Evidence`` attributes read them lazily)."""
+        self._close_readers()
         self.plan.trim()

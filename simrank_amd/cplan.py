@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._query import SolverQueries
 from .driver import LocalWorld, lean_knobs
 
 
@@ -62,7 +63,7 @@ def _prior32(spec):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class PlanSolver:
+class PlanSolver(SolverQueries):
     """``driver.Solver``'s surface over ``engine.Plan`` / ``engine.BiPlan``."""
 
     mode = "sparse"
@@ -128,6 +129,11 @@ class PlanSolver:
         cnt = self.plan.evidence_counts(j + 1) if self.bipartite else self.plan.evidence_counts()
         return 1 - 0.5 ** cnt.astype(np.float64)
 
+    def _make_reader(self, j):
+        """Node queries on a kept model (``_query.SolverQueries``): libsimrank_query.so on side j's iterate, in place."""
+        return self.plan.reader(j + 1) if self.bipartite else self.plan.reader()
+
     def release(self):
         """Free the matrices of the loop; the evidence counts stay (the ``Evidence`` attributes read them lazily)."""
+        self._close_readers()
         self.plan.trim()

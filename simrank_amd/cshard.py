@@ -21,6 +21,7 @@ import os
 
 import numpy as np
 
+from ._query import SolverQueries
 from .driver import LocalWorld, TorchWorld
 
 
@@ -97,7 +98,7 @@ def _prior32(spec):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
-class CShardSolver:
+class CShardSolver(SolverQueries):
     """The estimators' view of ``engine.ShardPlans`` / ``engine.ShardBiPlans``: the sharded loops behind the C ABI
     (csrc/shardplan.hip) — every class, f32 (the parity path) or, for SimRank / SimRank++ without a prior, fp16-held
     matrices."""
@@ -224,5 +225,10 @@ class CShardSolver:
             return out
         return self._share(out)
 
+    def _make_reader(self, j):
+        """Node queries on a kept model (``_query.SolverQueries``): libsimrank_query.so on side j's iterate, in place."""
+        return self.plans.reader(j + 1) if self.bipartite else self.plans.reader()
+
     def release(self):
+        self._close_readers()
         self.plans.free()

@@ -816,4 +816,15 @@ int simrank_f64_plan_trim(simrank_f64_plan* p) {
     return SIMRANK_F64_OK;
 }
 
+int simrank_f64_plan_get(const simrank_f64_plan* p, int32_t side, const char* key, int64_t* value) {
+    F64_REQUIRE(p && key && value, "plan, key or value is NULL");
+    F64_REQUIRE(side >= 0 && side < p->ns, "side %d out of range (the plan has %d)", (int)side, (int)p->ns);
+    const Side& s = p->s[side];
+    if (!std::strcmp(key, "iterate")) *value = p->released ? 0 : (int64_t)(uintptr_t)s.S[s.cur];
+    else if (!std::strcmp(key, "iterate_ld")) *value = s.ld;
+    else if (!std::strcmp(key, "iterate_rows")) *value = s.n;
+    else F64_REQUIRE(false, "unknown key '%s'", key);
+    return SIMRANK_F64_OK;
+}
+
 }  // extern "C"

@@ -137,6 +137,24 @@ def _iterate_block(get) -> dict:
                 cols=get("iterate_col_hi") - lo, row_ids=ids, col_ids=ids + 4 * lo)
 
 
+def _query_reader(ops, getters):
+    """``_query.Reader`` (libsimrank_query.so: rows, pairs and top-k of CHOSEN nodes) over the current iterate of the plans
+    behind ``getters`` (one per column block; all share the rows and the solver's order, "ids", which is read back once)."""
+    from . import _query
+    blocks = []
+    for get in getters:
+        b = _iterate_block(get)
+        b["col_lo"] = get("iterate_col_lo")
+        blocks.append(b)
+    n = blocks[0]["rows"]
+    order = np.empty(n, dtype=np.int32)
+    if n:
+        check(ops.lib.simrank_memcpy_d2h(order.ctypes.data, C.c_void_p(blocks[0]["row_ids"]), 4 * n, ops.stream),
+              "simrank_memcpy_d2h")
+        check(ops.lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+    return _query.Reader(ops, blocks, order)
+
+
 class Selection:
     """The two passes of libsimrank_select.so over blocks of one iterate that share their rows (a plan's matrix, or the
     column blocks of this process's ranks) on ``ops``' stream.  Constructing it runs the COUNT pass and scans the counts
@@ -336,6 +354,10 @@ class Plan:
         """The count pass of ``pairs_above`` (``Selection``): the current iterate, read in place."""
         return Selection(self.ops, [_iterate_block(self.get)], t, timing)
 
+    def reader(self):
+        """Node queries on the current iterate, read in place (``_query.Reader``).  Before ``trim``."""
+        return _query_reader(self.ops, [self.get])
+
     def pairs_above(self, t, max_pairs=2 ** 27):
         """(offsets int64 [n + 1], neighbour ids int32, values float32): row i (caller's order) lists the OTHER nodes c
         with float64(S[i][c]) >= t, ascending — the masked ``np.nonzero`` of the dense result.  ValueError, with nothing
@@ -489,6 +511,11 @@ class ShardPlans:
         lib = self.ops.lib
         return Selection(self.ops, [_iterate_block(lambda k, h=h: _shardplan_get(lib, h, k)) for h in self.plans], t,
                          timing)
+
+    def reader(self):
+        """Node queries over the column blocks of this process's plans (``_query.Reader``)."""
+        lib = self.ops.lib
+        return _query_reader(self.ops, [lambda k, h=h: _shardplan_get(lib, h, k) for h in self.plans])
 
     def pairs_above(self, t, max_pairs=2 ** 27):
         """As ``Plan.pairs_above``, over the column blocks of this process's plans (the whole matrix in an in-process
@@ -650,6 +677,11 @@ class ShardBiPlans:
         return Selection(self.ops, [_iterate_block(lambda k, h=h: _shardplan_get(lib, C.c_void_p(h), k))
                                     for h in self._sides[group]], t, timing)
 
+    def reader(self, group: int):
+        """Node queries on group 1 | 2's column blocks (``_query.Reader``)."""
+        lib = self.ops.lib
+        return _query_reader(self.ops, [lambda k, h=h: _shardplan_get(lib, C.c_void_p(h), k) for h in self._sides[group]])
+
     def pairs_above(self, group: int, t, max_pairs=2 ** 27):
         """As ``ShardPlans.pairs_above``, for group 1 | 2."""
         return _pairs_above(self.selection(group, t), max_pairs)
@@ -750,6 +782,10 @@ class BiPlan:
 
     def selection(self, group: int, t, timing: bool = False) -> Selection:
         return Selection(self.ops, [_iterate_block(lambda k: self.get(group, k))], t, timing)
+
+    def reader(self, group: int):
+        """Node queries on group 1 | 2's current iterate (``_query.Reader``).  Before ``trim``."""
+        return _query_reader(self.ops, [lambda k: self.get(group, k)])
 
     def pairs_above(self, group: int, t, max_pairs=2 ** 27):
         """As ``Plan.pairs_above``, for group 1 | 2."""

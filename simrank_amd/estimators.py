@@ -30,6 +30,11 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
                       "fp16" is BASELINE.json config 5's reduced-precision dense leg, outside the parity bar
     storage_precision "f32" (default) | "fp16" (config 5's matrices held in fp16, outside the parity bar) | "f64"
                       (the reference's float64 loop on one GPU: libsimrank_f64.so; every hand-back float64)
+    keep              False (default) | True: hand nothing back, keep the model on the device and return the estimator
+                      itself, which then answers node queries without the N x N transfer (``_KeptModel``: ``rows``,
+                      ``similarity``, ``most_similar``, ``frame``, ``top_k``, ``pairs``, ``release``; a context manager).
+                      One GPU or ``LocalWorld(P)``, every storage precision; not with ``top_k`` / ``min_similarity``
+                      (the kept model answers them)
     strict_reference  bipartite classes only; True keeps quirks Q1 (set-order labels on
                       sorted-order data) and Q2 (Evidence_N1 on the group-2 update, a
                       ValueError when n1 != n2); False labels correctly and uses Evidence_N2
@@ -258,7 +263,147 @@ def _is_symmetric(prior) -> bool:
     return a.ndim == 2 and a.shape[0] == a.shape[1] and bool(np.array_equal(a, a.T))
 
 
-class SimRank(object):
+def _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, ops_factory):
+    """``fit(keep=...)`` checked before any device work (ValueError)."""
+    if not isinstance(keep, bool):
+        raise ValueError(f"keep must be True or False, not {keep!r}")
+    if not keep:
+        return
+    if top_k or min_similarity is not None:
+        raise ValueError("keep=True hands nothing back: ask the kept model instead (most_similar / top_k(k) / pairs(t)), "
+                         "not fit(top_k=..., min_similarity=...)")
+    from .driver import TorchWorld
+    if isinstance(world, TorchWorld):
+        raise ValueError("keep=True runs on one GPU or on LocalWorld(P): on a TorchWorld every query would have to be a "
+                         "collective call on all ranks")
+    if ops_factory is not None or mode in ("dense", "hybrid") or getattr(world, "loop", "c") == "python":
+        raise ValueError("keep=True needs a solver behind the C ABI (mode 'auto' / 'sparse', no injected engine, no "
+                         "loop='python' world): the kept model is read in place by libsimrank_query.so")
+
+
+class _KeptModel:
+    """What ``fit(keep=True)`` leaves on an estimator: the solver with its iterate on the device, and the queries on it.
+    ``nodes`` are the caller's labels, in any order, repeats allowed (KeyError for an unknown one); bipartite classes take
+    ``group=1 | 2`` and label as their ``fit`` did.  Every value is bit-identical to the same element of what the same
+    ``fit`` without ``keep`` returns.  The model holds its whole plan (three N x N matrices per side plus prior and
+    counts) until ``release()``, the end of a ``with`` block, a second ``fit`` or the estimator's collection."""
+
+    _model = None              # (solver, [(side j, labels)]) of a kept fit
+    _model_released = False
+
+    def _keep(self, solver, sides):
+        self._model = (solver, [(j, list(lab) if not isinstance(lab, list) else lab) for j, lab in sides])
+        self._model_released = False
+        self._indexes = {}
+        return self
+
+    def _kept(self, group=None):
+        if self._model is None:
+            if self._model_released:
+                raise RuntimeError("the kept model was released (release(), the end of a with block, or a second fit): "
+                                   "fit(keep=True) again")
+            raise RuntimeError("there is no kept model: call fit(..., keep=True) first")
+        solver, sides = self._model
+        if len(sides) == 1:
+            if group not in (None, 1):
+                raise ValueError(f"this class has one node group: group must be None or 1, not {group!r}")
+            s = 0
+        else:
+            if group not in (1, 2):
+                raise ValueError(f"group must be 1 or 2, not {group!r}")
+            s = group - 1
+        j, labels = sides[s]
+        return solver, j, labels
+
+    def _ids(self, s, labels, nodes):
+        """The caller ids (positions in the dense frame's label order) of ``nodes``."""
+        index = self._indexes.get(s)
+        if index is None:
+            index = self._indexes[s] = pd.Index(labels)
+        nodes = list(nodes)
+        if not nodes:
+            return index, np.empty(0, dtype=np.int32)
+        ids = index.get_indexer(pd.Index(nodes, dtype=object) if index.dtype == object else pd.Index(nodes))
+        if (ids < 0).any():
+            raise KeyError(nodes[int(np.argmax(ids < 0))])
+        return index, ids.astype(np.int32)
+
+    def rows(self, nodes, group=None):
+        """DataFrame, index = ``nodes`` as given, columns = the dense frame's: ``dense.loc[nodes]``, read on the device."""
+        solver, j, labels = self._kept(group)
+        index, ids = self._ids(j, labels, nodes)
+        return pd.DataFrame(solver.rows(j, ids), index=index.take(ids), columns=index.copy())
+
+    def similarity(self, a, b, group=None):
+        """float64 ndarray: element i is ``dense.at[a[i], b[i]]`` (``a`` and ``b`` label sequences of equal length)."""
+        a, b = list(a), list(b)
+        if len(a) != len(b):
+            raise ValueError(f"a and b must have the same length ({len(a)} != {len(b)})")
+        solver, j, labels = self._kept(group)
+        _, ia = self._ids(j, labels, a)
+        _, ib = self._ids(j, labels, b)
+        return solver.pair_values(j, ia, ib)
+
+    def most_similar(self, nodes, k, group=None):
+        """Long frame (node, rank, neighbor, similarity): the rows of the ``fit(top_k=k)`` frame of the nodes in ``nodes``,
+        blocks in the order of ``nodes``."""
+        from ._query import check_k
+        k = check_k(k)
+        solver, j, labels = self._kept(group)
+        lab, ids = self._ids(j, labels, nodes)
+        idx, val = solver.topk_of(j, ids, k)
+        n, kk = idx.shape
+        keep = idx.ravel() >= 0
+        return pd.DataFrame({
+            "node": lab.take(np.repeat(ids.astype(np.intp), kk)[keep]),
+            "rank": np.tile(np.arange(1, kk + 1), n)[keep],
+            "neighbor": lab.take(idx.ravel()[keep]),
+            "similarity": val.ravel()[keep]})
+
+    def _all_sides(self, make):
+        self._kept(1)
+        solver, sides = self._model
+        out = [make(solver, j, lab) for j, lab in sides]
+        return out[0] if len(sides) == 1 else tuple(out)
+
+    def frame(self):
+        """What ``fit`` without ``keep`` returns: the dense frame (a tuple of two for the bipartite classes)."""
+        return self._all_sides(lambda solver, j, lab: _square_frame(solver.result(j), lab))
+
+    def top_k(self, k):
+        """What ``fit(top_k=k)`` returns."""
+        from ._query import check_k
+        k = check_k(k)
+        return self._all_sides(lambda solver, j, lab: _topk_frame(solver, j, k, lab))
+
+    def pairs(self, min_similarity, max_pairs=2 ** 27):
+        """What ``fit(min_similarity=t, max_pairs=m)`` returns."""
+        _check_pairs_args(min_similarity, max_pairs)
+        return self._all_sides(lambda solver, j, lab: _pairs_frame(solver, j, min_similarity, max_pairs, lab))
+
+    def release(self):
+        """Free the kept model's device memory (the lazy ``Evidence`` attributes keep working); queries raise afterwards."""
+        if self._model is not None:
+            solver = self._model[0]
+            self._model = None
+            self._model_released = True
+            solver.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.release()
+        return False
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+class SimRank(_KeptModel):
     """SimRank on a directed, optionally weighted graph (SimRank.py:8-141).
 
     Attributes after ``fit``: ``Nodes`` (set), ``Graph`` (N x N DataFrame, built on read),
@@ -283,9 +428,11 @@ class SimRank(object):
     def _side(self, csr, C):
         return SideSpec(csr, csr.rowscale, C)
 
-    def _finish(self, solver, k, top_k=None, min_similarity=None, max_pairs=2 ** 27):
+    def _finish(self, solver, k, top_k=None, min_similarity=None, max_pairs=2 ** 27, keep=False):
         self.converged_at = k
         self.engine_mode = solver.mode
+        if keep:
+            return self._keep(solver, [(0, self._order)])
         if min_similarity is not None:
             return _result_frames(solver, [(0, self._order)], top_k, min_similarity, max_pairs)[0]
         if top_k:
@@ -301,13 +448,15 @@ class SimRank(object):
     def fit(self, data, C=0.8, weighted=False, from_node_column="from", to_node_column="to",
             weight_column="weight", iterations=100, eps=1e-4, verbose=True, *,
             mode="auto", device=None, world=None, top_k=None, min_similarity=None, max_pairs=2 ** 27,
-            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            dense_precision="f32", storage_precision="f32", keep=False, _ops_factory=None):
         _check_pairs_args(min_similarity, max_pairs)
+        _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, _ops_factory)
+        self.release()
         with _precision(dense_precision, storage_precision):
             csr = self._create_graph(data, weighted, from_node_column, to_node_column, weight_column)
             solver, k = _solve([self._side(csr, C)], iterations, eps, verbose, mode, device, world,
                                _ops_factory)
-            return self._finish(solver, k, top_k, min_similarity, max_pairs)
+            return self._finish(solver, k, top_k, min_similarity, max_pairs, keep)
 
 
 class SimRankPP(SimRank):
@@ -337,7 +486,7 @@ class SimRankPP(SimRank):
 
     def _fit_pp(self, data, C, weighted, from_node_column, to_node_column, weight_column,
                 iterations, eps, verbose, mode, device, world, ops_factory, apriori=None,
-                lbd=0.0, top_k=None, min_similarity=None, max_pairs=2 ** 27):
+                lbd=0.0, top_k=None, min_similarity=None, max_pairs=2 ** 27, keep=False):
         csr = self._create_graph(data, weighted, from_node_column, to_node_column, weight_column)
         talk = verbose and (world is None or world.is_root)
         spec = self._pp_side(csr, C, talk, apriori, lbd)
@@ -357,17 +506,19 @@ class SimRankPP(SimRank):
                        on_iteration=(lambda i: update_progress(i / iterations)) if talk else None,
                        on_converged=announce_converged if talk else None)
         self.Evidence = _lazy_evidence(world, solver, 0, csr)
-        return self._finish(solver, k, top_k, min_similarity, max_pairs)
+        return self._finish(solver, k, top_k, min_similarity, max_pairs, keep)
 
     def fit(self, data, C=0.8, weighted=False, from_node_column="from", to_node_column="to",
             weight_column="weight", iterations=100, eps=1e-4, verbose=True, *,
             mode="auto", device=None, world=None, top_k=None, min_similarity=None, max_pairs=2 ** 27,
-            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            dense_precision="f32", storage_precision="f32", keep=False, _ops_factory=None):
         _check_pairs_args(min_similarity, max_pairs)
+        _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, _ops_factory)
+        self.release()
         with _precision(dense_precision, storage_precision):
             return self._fit_pp(data, C, weighted, from_node_column, to_node_column, weight_column,
                                 iterations, eps, verbose, mode, device, world, _ops_factory,
-                                top_k=top_k, min_similarity=min_similarity, max_pairs=max_pairs)
+                                top_k=top_k, min_similarity=min_similarity, max_pairs=max_pairs, keep=keep)
 
 
 class AprioriSimRank(SimRankPP):
@@ -379,8 +530,10 @@ class AprioriSimRank(SimRankPP):
     def fit(self, data, AprioriSim, C=0.8, lbd=0.5, weighted=False, from_node_column="from",
             to_node_column="to", weight_column="weight", iterations=100, eps=1e-4,
             verbose=True, *, mode="auto", device=None, world=None, top_k=None, min_similarity=None,
-            max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32", keep=False, _ops_factory=None):
         _check_pairs_args(min_similarity, max_pairs)
+        _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, _ops_factory)
+        self.release()
         with _precision(dense_precision, storage_precision):
             if not isinstance(AprioriSim, np.ndarray):
                 # the reference fails at np.fill_diagonal for anything but an ndarray
@@ -388,13 +541,13 @@ class AprioriSimRank(SimRankPP):
             return self._fit_pp(data, C, weighted, from_node_column, to_node_column, weight_column,
                                 iterations, eps, verbose, mode, device, world, _ops_factory,
                                 apriori=AprioriSim, lbd=lbd, top_k=top_k, min_similarity=min_similarity,
-                                max_pairs=max_pairs)
+                                max_pairs=max_pairs, keep=keep)
 
 
 # ----------------------------------------------------------------------------------------
 # bipartite
 # ----------------------------------------------------------------------------------------
-class BipartiteSimRank(object):
+class BipartiteSimRank(_KeptModel):
     """SimRank on a bipartite graph: two similarity matrices updated alternately, the
     second from the just-updated first (SimRank.py:143-303)."""
     Graph_N1_N2 = _Lazy("Graph_N1_N2", pd.DataFrame)
@@ -418,10 +571,12 @@ class BipartiteSimRank(object):
         self.Graph_N2_N1 = lambda: pd.DataFrame(g21.dense(), index=lab2, columns=lab1)
         return g12, g21
 
-    def _finish(self, solver, k, strict_reference, top_k=None, min_similarity=None, max_pairs=2 ** 27):
+    def _finish(self, solver, k, strict_reference, top_k=None, min_similarity=None, max_pairs=2 ** 27, keep=False):
         self.converged_at = k
         self.engine_mode = solver.mode
         l1, l2 = self._set_order if strict_reference else map(list, self._sorted)
+        if keep:
+            return self._keep(solver, [(0, l1), (1, l2)])
         if min_similarity is not None:
             out = _result_frames(solver, [(0, l1), (1, l2)], top_k, min_similarity, max_pairs)
             return None if out[0] is None else tuple(out)
@@ -439,14 +594,16 @@ class BipartiteSimRank(object):
             node_group2_column="item", weight_column="weight", iterations=100, eps=1e-4,
             verbose=True, *, mode="auto", device=None, world=None, strict_reference=True,
             top_k=None, min_similarity=None, max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32",
-            _ops_factory=None):
+            keep=False, _ops_factory=None):
         _check_pairs_args(min_similarity, max_pairs)
+        _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, _ops_factory)
+        self.release()
         with _precision(dense_precision, storage_precision):
             g12, g21 = self._create_graph(data, weighted, node_group1_column, node_group2_column,
                                           weight_column)
             specs = [SideSpec(g12, g12.rowscale, C1), SideSpec(g21, g21.rowscale, C2)]
             solver, k = _solve(specs, iterations, eps, verbose, mode, device, world, _ops_factory)
-            return self._finish(solver, k, strict_reference, top_k, min_similarity, max_pairs)
+            return self._finish(solver, k, strict_reference, top_k, min_similarity, max_pairs, keep)
 
 
 class BipartiteSimRankPP(SimRankPP):
@@ -471,7 +628,7 @@ class BipartiteSimRankPP(SimRankPP):
     def _fit_bpp(self, data, C1, C2, weighted, node_group1_column, node_group2_column,
                  weight_column, iterations, eps, verbose, mode, device, world, strict_reference,
                  ops_factory, priors=(None, None), lbds=(0.0, 0.0), top_k=None, min_similarity=None,
-                 max_pairs=2 ** 27):
+                 max_pairs=2 ** 27, keep=False):
         g12, g21 = self._create_graph(data, weighted, node_group1_column, node_group2_column,
                                       weight_column)
         world = world or LocalWorld(1)
@@ -505,19 +662,21 @@ class BipartiteSimRankPP(SimRankPP):
         self.Evidence_N1 = _lazy_evidence(world, solver, 0, g12)
         self.Evidence_N2 = ((lambda: _host_evidence(g21)) if strict_reference
                             else _lazy_evidence(world, solver, 1, g21))
-        return self._finish(solver, k, strict_reference, top_k, min_similarity, max_pairs)
+        return self._finish(solver, k, strict_reference, top_k, min_similarity, max_pairs, keep)
 
     def fit(self, data, C1=0.8, C2=0.8, weighted=False, node_group1_column="user",
             node_group2_column="item", weight_column="weight", iterations=100, eps=1e-4,
             verbose=True, *, mode="auto", device=None, world=None, strict_reference=True,
             top_k=None, min_similarity=None, max_pairs=2 ** 27, dense_precision="f32", storage_precision="f32",
-            _ops_factory=None):
+            keep=False, _ops_factory=None):
         _check_pairs_args(min_similarity, max_pairs)
+        _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, _ops_factory)
+        self.release()
         with _precision(dense_precision, storage_precision):
             return self._fit_bpp(data, C1, C2, weighted, node_group1_column, node_group2_column,
                                  weight_column, iterations, eps, verbose, mode, device, world,
                                  strict_reference, _ops_factory, top_k=top_k, min_similarity=min_similarity,
-                                 max_pairs=max_pairs)
+                                 max_pairs=max_pairs, keep=keep)
 
 
 class BipartitleAprioriSimRank(BipartiteSimRankPP):
@@ -531,8 +690,10 @@ class BipartitleAprioriSimRank(BipartiteSimRankPP):
             weighted=False, node_group1_column="user", node_group2_column="item",
             weight_column="weight", iterations=100, eps=1e-4, verbose=True, *, mode="auto",
             device=None, world=None, strict_reference=True, top_k=None, min_similarity=None, max_pairs=2 ** 27,
-            dense_precision="f32", storage_precision="f32", _ops_factory=None):
+            dense_precision="f32", storage_precision="f32", keep=False, _ops_factory=None):
         _check_pairs_args(min_similarity, max_pairs)
+        _check_keep(keep, top_k, min_similarity, world, storage_precision, mode, _ops_factory)
+        self.release()
         with _precision(dense_precision, storage_precision):
             for a in (AprioriSim1, AprioriSim2):
                 if not isinstance(a, np.ndarray):
@@ -541,7 +702,7 @@ class BipartitleAprioriSimRank(BipartiteSimRankPP):
                                  weight_column, iterations, eps, verbose, mode, device, world,
                                  strict_reference, _ops_factory, priors=(AprioriSim1, AprioriSim2),
                                  lbds=(lbd1, lbd2), top_k=top_k, min_similarity=min_similarity,
-                                 max_pairs=max_pairs)
+                                 max_pairs=max_pairs, keep=keep)
 
 
 def _lazy_evidence(world, solver, j, csr):
