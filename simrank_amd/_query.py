@@ -97,6 +97,7 @@ class SolverQueries:
     with: one ``Reader`` per side, made on first use by the solver's ``_make_reader(j)`` and closed at ``release``."""
 
     _readers = None
+    _folders = None
 
     def _reader(self, j):
         if self._readers is None:
@@ -119,7 +120,27 @@ class SolverQueries:
         k = int(min(k, max(1, self.n[j] - 1)))
         return self._reader(j).topk_of(node_ids, k)
 
+    def fold_in(self, j, lists, w, prior=None, top_k=None, timing=None):
+        """Rows of NEW nodes joining side j (``_foldin.Folder.run``): ``lists`` hold ids of the side the update reads
+        (the same side for the one-matrix classes, the other one for the bipartite classes).  Side j's CSR goes to the
+        device at the first call and stays until ``release``."""
+        from . import _foldin
+        if self._folders is None:
+            self._folders = {}
+        if j not in self._folders:
+            spec = self.specs[j]
+            evidence = spec.evidence_from is not None
+            if evidence and spec.evidence_from is not spec.csr:
+                _foldin.check_strict_group(len(self.specs), j, True)
+                raise ValueError("fold_in needs the evidence of the side's own pattern")
+            src = len(self.specs) - 1 - j
+            self._folders[j] = _foldin.Folder(self._reader(src), spec.csr, spec.rowscale, spec.coef, spec.lbd, evidence)
+        return self._folders[j].run(lists, w, prior, top_k, timing)
+
     def _close_readers(self):
+        folders, self._folders = self._folders or {}, None
+        for f in folders.values():
+            f.close()
         readers, self._readers = self._readers or {}, None
         for r in readers.values():
             r.close()

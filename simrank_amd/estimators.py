@@ -32,7 +32,8 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
                       (the reference's float64 loop on one GPU: libsimrank_f64.so; every hand-back float64)
     keep              False (default) | True: hand nothing back, keep the model on the device and return the estimator
                       itself, which then answers node queries without the N x N transfer (``_KeptModel``: ``rows``,
-                      ``similarity``, ``most_similar``, ``frame``, ``top_k``, ``pairs``, ``release``; a context manager).
+                      ``similarity``, ``most_similar``, ``fold_in`` (nodes that were NOT in the graph), ``frame``,
+                      ``top_k``, ``pairs``, ``release``; a context manager).
                       One GPU or ``LocalWorld(P)``, every storage precision; not with ``top_k`` / ``min_similarity``
                       (the kept model answers them)
     strict_reference  bipartite classes only; True keeps quirks Q1 (set-order labels on
@@ -360,6 +361,55 @@ class _KeptModel:
             "neighbor": lab.take(idx.ravel()[keep]),
             "similarity": val.ravel()[keep]})
 
+    def fold_in(self, neighbors, weights=None, prior=None, names=None, group=None, top_k=None):
+        """Similarities of nodes that were NOT in the fitted graph: for each new node, the row the NEXT update would
+        compute for a node with that neighbour list, with every existing similarity and every existing normalisation
+        held fixed (a new group-1 node does NOT change the normalisation of its items: that is what makes the answer one
+        update and not a refit):
+
+            s(q, b) = [(1 - lbd)] * E(q, b) * C * sum_{i in I_q} w_q * sum_{j in I(b)} S[i, j] * W[b, j]  [+ lbd * prior(q, b)]
+
+        ``neighbors``: one sequence of labels of FITTED nodes per new node: its in-neighbours (the ``from`` nodes of its
+        edges) for the directed classes; for the bipartite classes ``group=1`` is a new group-1 node given by its group-2
+        neighbours, ``group=2`` the other way round.  ``weights`` (exactly when the fit had ``weighted=True``): one
+        sequence per new node; every entry of the new row is 1 / sum(weights), as the reference scales a row (0 where that
+        is not finite); unweighted 1 / len(list); an empty list gives a row of zeros.  ``prior`` (classes fitted with a
+        prior): array [n_new, N] in the dense frame's column order (default zeros).  ``names``: the index of the result.
+        SimRank++ classes count the evidence |I_q ∩ I(b)| on the device from the new list.
+
+        -> DataFrame [n_new x N] float64, columns as the dense frame's; with ``top_k=k`` the long frame (node, rank,
+        neighbor, similarity) of the k best per new node (value descending, label position ascending; no node is
+        excluded: a new node has no diagonal), selected on the device; k is clamped to N and may then be at most 1024
+        (the selection kernel's limit: ValueError before any device work)."""
+        from . import _foldin
+        if self._model is None:
+            self._kept(1)                                   # (raises: no kept model, or released)
+        solver, sides = self._model
+        side = _foldin.side_of(len(sides), group)
+        specs = getattr(solver, "specs", None)
+        strict = bool(specs and len(specs) == 2 and specs[1].evidence_from is not None
+                      and specs[1].evidence_from is specs[0].csr)
+        _foldin.check_strict_group(len(sides), side, strict)
+        j, labels = sides[side]
+        src_j, src_labels = sides[len(sides) - 1 - side]
+        src_index, _ = self._ids(src_j, src_labels, [])
+        out_index, _ = self._ids(j, labels, [])
+        lists, w, prior, names, k = _foldin.prepare(
+            neighbors, src_index, n_out=len(out_index), weighted=bool(getattr(self, "_weighted", False)),
+            has_prior=bool(specs and specs[side].apriori is not None), weights=weights, prior=prior, names=names,
+            top_k=top_k)
+        new_index = pd.RangeIndex(len(lists)) if names is None else pd.Index(names)
+        if k is None:
+            return pd.DataFrame(solver.fold_in(j, lists, w, prior), index=new_index, columns=out_index.copy())
+        idx, val = solver.fold_in(j, lists, w, prior, top_k=k)
+        n, kk = idx.shape
+        keep = idx.ravel() >= 0
+        return pd.DataFrame({
+            "node": new_index.take(np.repeat(np.arange(n), kk)[keep]),
+            "rank": np.tile(np.arange(1, kk + 1), n)[keep],
+            "neighbor": out_index.take(idx.ravel()[keep]),
+            "similarity": val.ravel()[keep]})
+
     def _all_sides(self, make):
         self._kept(1)
         solver, sides = self._model
@@ -419,6 +469,7 @@ class SimRank(_KeptModel):
     def _create_graph(self, data, weighted, from_node_column, to_node_column, weight_column):
         nodes, csr = ingest.directed(data, weighted, from_node_column, to_node_column,
                                      weight_column)
+        self._weighted = bool(weighted)                     # (fold_in asks for weights exactly when the fit had them)
         self.Nodes = set(nodes)
         self._order = nodes
         self._csr = csr
@@ -563,6 +614,7 @@ class BipartiteSimRank(_KeptModel):
                       weight_column):
         set1, set2, lab1, lab2, g12, g21 = ingest.bipartite(
             data, weighted, node_group1_column, node_group2_column, weight_column)
+        self._weighted = bool(weighted)
         self.NodesGroup1, self.NodesGroup2 = set(set1), set(set2)
         self._set_order = (set1, set2)
         self._sorted = (lab1, lab2)
