@@ -25,10 +25,13 @@
  *   Every normalised adjacency the reference builds has this form (SimRank.py:45-52,
  *   :191-200: each stored value is 1/in-degree or 1/sum-of-weights of its ROW node; the
  *   SimRank++ "spread" factor of :326-333 is again per row).
- *   One similarity update  S' = coef . W . S . W^T (.*E) (+ lbd.A), diag <- 1  is two calls
- *   of simrank_spmm:   Tt = (W . S)^T      (transpose_out = 1, no epilogue)
- *                      S' = W . Tt          (epilogue)            [S symmetric]
- *   or, for dense graphs, simrank_spmm / simrank_gemm_nt on a densified W (MFMA).
+ *   One similarity update  S' = coef . W . S . W^T (.*E) (+ lbd.A), diag <- 1  is two legs:
+ *                      Tt = (W . S)^T      (leg 1: transposed out, no epilogue)
+ *                      S' = W . Tt          (leg 2: epilogue)     [S symmetric]
+ *   The plans (simrank_plan_*, simrank_biplan_*, simrank_shardplan_*) queue both legs and the
+ *   convergence count of an update in one call: they are what fit() runs.  The kernel-level
+ *   entries run one leg per call (simrank_spmm and its blocked / fp16 / shard forms;
+ *   simrank_gemm_nt on a densified W for dense graphs) and serve tests and measurements.
  */
 #ifndef SIMRANK_HIP_H
 #define SIMRANK_HIP_H

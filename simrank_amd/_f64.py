@@ -7,11 +7,8 @@ fallback: a missing library or device is an error.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsimrank_f64.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simrank_f64.h")
+from ._companion import Companion
 
 VERSION = 1              # SIMRANK_F64_VERSION of include/simrank_f64.h
 ERR_INVALID, ERR_HIP, ERR_MEMORY = -1, -2, -3
@@ -58,26 +55,5 @@ class F64MemoryError(F64Error, MemoryError):
     """The device has too little free memory for an f64 plan."""
 
 
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise F64Error(f"{LIB_PATH} is missing: build it with `make -C simrank_amd/csrc` (no CPU fallback)")
-        lib = C.CDLL(LIB_PATH)
-        for name, argtypes in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        if lib.simrank_f64_version() != VERSION:
-            raise F64Error(f"libsimrank_f64.so version {lib.simrank_f64_version()} != {VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check(rc: int, what: str):
-    if rc != 0:
-        msg = load().simrank_f64_last_error().decode(errors="replace")
-        raise (F64MemoryError if rc == ERR_MEMORY else F64Error)(f"{what} failed ({rc}): {msg}")
+_c = Companion("f64", VERSION, PROTOTYPES, _RESTYPES, F64Error, {ERR_MEMORY: F64MemoryError})
+LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.check

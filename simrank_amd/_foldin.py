@@ -9,13 +9,10 @@ library or device is an error.
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import numpy as np
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsimrank_foldin.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simrank_foldin.h")
+from ._companion import ROWMAJOR_F64, Companion
 
 VERSION = 1              # SIMRANK_FOLDIN_VERSION of include/simrank_foldin.h
 TILE = 32                # SIMRANK_FOLDIN_TILE: new nodes per gather / apply
@@ -44,29 +41,8 @@ class FoldInError(RuntimeError):
     """A call into libsimrank_foldin.so failed."""
 
 
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise FoldInError(f"{LIB_PATH} is missing: build it with `make -C simrank_amd/csrc` (no CPU fallback)")
-        lib = C.CDLL(LIB_PATH)
-        for name, argtypes in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        if lib.simrank_foldin_version() != VERSION:
-            raise FoldInError(f"libsimrank_foldin.so version {lib.simrank_foldin_version()} != {VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check(rc: int, what: str):
-    if rc != 0:
-        msg = load().simrank_foldin_last_error().decode(errors="replace")
-        raise FoldInError(f"{what} failed ({rc}): {msg}")
+_c = Companion("foldin", VERSION, PROTOTYPES, _RESTYPES, FoldInError)
+LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.check
 
 
 # ---- the host half: arguments ----------------------------------------------------------------------------------------
@@ -192,7 +168,7 @@ class Folder:
     def _buf(self, name, nbytes):
         ptr, cap = self._bufs.get(name, (None, 0))
         if cap < nbytes:
-            self.reader._sync()
+            self.ops.synchronize()
             if ptr:
                 check(self.f.simrank_foldin_free(ptr), "simrank_foldin_free")
             self._bufs.pop(name, None)
@@ -203,15 +179,12 @@ class Folder:
         return ptr
 
     def _put(self, name, host):
-        from .engine import check as hip_check
         ptr = self._buf(name, host.nbytes)
-        if host.size:
-            hip_check(self.ops.lib.simrank_memcpy_h2d(C.c_void_p(ptr), host.ctypes.data, host.nbytes, self.ops.stream),
-                      "simrank_memcpy_h2d")
+        self.ops.h2d(ptr, host)
         return ptr
 
     def _drop(self, keep=()):
-        self.reader._sync()
+        self.ops.synchronize()
         for name in [n for n in self._bufs if n not in keep]:
             check(self.f.simrank_foldin_free(self._bufs.pop(name)[0]), "simrank_foldin_free")
 
@@ -223,7 +196,7 @@ class Folder:
         float64 [n_new, n_out], or with ``top_k`` (ids int32 [n_new, k], values float64 [n_new, k]) selected on the
         device.  ``timing``: a dict that receives the milliseconds of the stages (HIP events; serialises them)."""
         from . import _query, hostpool
-        from ._query import SLAB_BYTES, _timed
+        from ._query import SLAB_BYTES
         ops, rd, n_out, n_src = self.ops, self.reader, self.n_out, self.n_src
         n_new = len(lists)
         k = None if top_k is None else int(min(top_k, max(1, n_out)))
@@ -241,7 +214,7 @@ class Folder:
             if timing is None:
                 launch()
             else:
-                timing[name] = timing.get(name, 0.0) + _timed(ops, launch)
+                timing[name] = timing.get(name, 0.0) + ops.timed(launch)
 
         try:
             T = dev("T", t_bytes)
@@ -279,7 +252,7 @@ class Folder:
                         member, self.coef, self.lbd, None if prior_dev is None else prior_dev + 8 * (t0 - q0) * n_out,
                         n_out, nt, slab + 8 * (t0 - q0) * n_out, n_out, ops.stream), "simrank_foldin_apply"))
                 if k is None:
-                    rd._d2h(result[q0:q0 + m], slab, 8 * m * n_out)
+                    ops.d2h(result[q0:q0 + m], slab)
                 else:
                     # the k best of each new row on the device: the result as a float64 row-major block, positions = ids,
                     # no node excluded (a new node has no diagonal)
@@ -287,16 +260,16 @@ class Folder:
                     nobody = up("nobody", np.full(m, -1, dtype=np.int32))
                     idx_dev, val_dev = dev("idx", 4 * m * k), dev("val", 8 * m * k)
                     stage("topk_ms", lambda: _query.check(rd.q.simrank_query_topk(
-                        slab, _query.ROWMAJOR_F64, n_out, m, n_out, rows, nobody, m, None, k, idx_dev, val_dev,
+                        slab, ROWMAJOR_F64, n_out, m, n_out, rows, nobody, m, None, k, idx_dev, val_dev,
                         ops.stream), "simrank_query_topk"))
-                    rd._d2h(result[0][q0:q0 + m], idx_dev, 4 * m * k)
-                    rd._d2h(result[1][q0:q0 + m], val_dev, 8 * m * k)
-                rd._sync()
+                    ops.d2h(result[0][q0:q0 + m], idx_dev)
+                    ops.d2h(result[1][q0:q0 + m], val_dev)
+                ops.synchronize()
         finally:
             # (what a large request needed does not stay with the model)
             big = [n for n, (_, cap) in self._bufs.items() if cap > KEEP_BYTES and n not in ("rowptr", "col", "scale")]
             if big:
                 self._drop(keep=[n for n in self._bufs if n not in big])
             else:
-                rd._sync()
+                ops.synchronize()
         return result

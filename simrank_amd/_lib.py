@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+from ._companion import bind
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (SIMRANK_LIB: an experiment build of the same ABI, tools/build_variant.sh; never set in production)
 LIB_PATH = os.environ.get("SIMRANK_LIB") or os.path.join(_HERE, "libsimrank_hip.so")
@@ -186,11 +188,7 @@ def load() -> C.CDLL:
             f"{LIB_PATH} not found: the HIP engine is not built.  Build it with "
             "`make -C simrank_amd/csrc` (or `python -c 'import __graft_entry__ as g; "
             "g.build()'`).  There is no CPU fallback.")
-    lib = C.CDLL(LIB_PATH)
-    for name, argtypes in PROTOTYPES.items():
-        fn = getattr(lib, name)          # AttributeError = symbol missing from the .so
-        fn.argtypes = argtypes
-        fn.restype = _RESTYPES.get(name, C.c_int)
+    lib = bind(C.CDLL(LIB_PATH), PROTOTYPES, _RESTYPES)          # AttributeError = symbol missing from the .so
     if lib.simrank_abi_version() != ABI_VERSION:
         raise ImportError("libsimrank_hip.so ABI version mismatch")
     _lib = lib

@@ -9,14 +9,10 @@ from __future__ import annotations
 
 import ctypes as C
 import numbers
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsimrank_query.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simrank_query.h")
+from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
 
 VERSION = 1              # SIMRANK_QUERY_VERSION of include/simrank_query.h
-PANEL_F32, ROWMAJOR_F32, PANEL_F16, ROWMAJOR_F64 = 0, 1, 2, 3
 
 SLAB_BYTES = 256 << 20   # device block of one band of ``rows`` (a larger request is cut into bands of query rows)
 
@@ -38,29 +34,8 @@ class QueryError(RuntimeError):
     """A call into libsimrank_query.so failed."""
 
 
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise QueryError(f"{LIB_PATH} is missing: build it with `make -C simrank_amd/csrc` (no CPU fallback)")
-        lib = C.CDLL(LIB_PATH)
-        for name, argtypes in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        if lib.simrank_query_version() != VERSION:
-            raise QueryError(f"libsimrank_query.so version {lib.simrank_query_version()} != {VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check(rc: int, what: str):
-    if rc != 0:
-        msg = load().simrank_query_last_error().decode(errors="replace")
-        raise QueryError(f"{what} failed ({rc}): {msg}")
+_c = Companion("query", VERSION, PROTOTYPES, _RESTYPES, QueryError)
+LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.check
 
 
 def check_k(k):
@@ -161,24 +136,6 @@ class Reader:
         self.inv[self.order] = np.arange(self.n, dtype=np.int32)
         self._maps = {}                                        # block index -> device int32 column map (made on first use)
 
-    # ---- device scratch ---------------------------------------------------------------------------------------------
-    def _upload_i32(self, host):
-        from .engine import check as hip_check
-        ptr = self.ops._malloc(max(4, 4 * host.size))
-        if host.size:
-            hip_check(self.ops.lib.simrank_memcpy_h2d(C.c_void_p(ptr), host.ctypes.data, 4 * host.size, self.ops.stream),
-                      "simrank_memcpy_h2d")
-        return ptr
-
-    def _d2h(self, host, ptr, nbytes):
-        from .engine import check as hip_check
-        hip_check(self.ops.lib.simrank_memcpy_d2h(host.ctypes.data, C.c_void_p(ptr), nbytes, self.ops.stream),
-                  "simrank_memcpy_d2h")
-
-    def _sync(self):
-        from .engine import check as hip_check
-        hip_check(self.ops.lib.simrank_stream_synchronize(self.ops.stream), "simrank_stream_synchronize")
-
     def _col_map(self, i):
         """Block i's columns in the caller's order: positions (within the block) sorted by caller id, on the device;
         with them the caller ids they go to (host).  One block holding every column: the inverse of the order."""
@@ -191,8 +148,8 @@ class Reader:
                 got = self._maps[i] = (None, ids)              # (the caller's order already: no map)
             else:
                 pos = np.ascontiguousarray(np.argsort(ids, kind="stable").astype(np.int32))
-                got = self._maps[i] = (self._upload_i32(pos), np.ascontiguousarray(ids[pos]))
-                self._sync()
+                got = self._maps[i] = (self.ops.put(pos), np.ascontiguousarray(ids[pos]))
+                self.ops.synchronize()
         return got
 
     def close(self):
@@ -215,7 +172,7 @@ class Reader:
             out = hostpool.empty_f64(n_q, n)
         if n_q == 0 or n == 0:
             return out
-        pos_dev = self._upload_i32(self.inv[node_ids])
+        pos_dev = ops.put(self.inv[node_ids])
         whole = len(self.blocks) == 1
         band = int(max(1, min(n_q, SLAB_BYTES // (8 * n))))
         slab = ops._malloc(8 * band * n)
@@ -232,19 +189,19 @@ class Reader:
                     if timing is None:
                         launch()
                     else:
-                        timing.append(_timed(ops, launch))
+                        timing.append(ops.timed(launch))
                     off += m * b["cols"]
                 if whole:
-                    self._d2h(out[q0:q0 + m], slab, 8 * m * n)
+                    ops.d2h(out[q0:q0 + m], slab, 8 * m * n)
                 else:
                     # every block's [m, cols] piece follows the other in the slab; its columns go to their caller ids
-                    self._d2h(stage, slab, 8 * m * n)
-                    self._sync()
+                    ops.d2h(stage, slab, 8 * m * n)
+                    ops.synchronize()
                     flat, off = stage.reshape(-1), 0
                     for i, b in enumerate(self.blocks):
                         out[q0:q0 + m, self._col_map(i)[1]] = flat[off:off + m * b["cols"]].reshape(m, b["cols"])
                         off += m * b["cols"]
-            self._sync()
+            ops.synchronize()
         finally:
             ops._free(slab)
             ops._free(pos_dev)
@@ -260,7 +217,7 @@ class Reader:
         out = np.empty(m, dtype=np.float64)
         if m == 0:
             return out
-        a_dev = self._upload_i32(a)
+        a_dev = ops.put(a)
         val_dev = ops._malloc(8 * m)
         try:
             for b in self.blocks:
@@ -271,13 +228,13 @@ class Reader:
                 if mine.size == m:
                     rows_dev, got = a_dev, out
                 else:
-                    rows_dev, got = self._upload_i32(np.ascontiguousarray(a[mine])), np.empty(mine.size, dtype=np.float64)
-                cols_dev = self._upload_i32(np.ascontiguousarray(bp[mine] - lo))
+                    rows_dev, got = ops.put(np.ascontiguousarray(a[mine])), np.empty(mine.size, dtype=np.float64)
+                cols_dev = ops.put(np.ascontiguousarray(bp[mine] - lo))
                 try:
                     check(self.q.simrank_query_pairs(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], rows_dev,
                                                      cols_dev, mine.size, val_dev, ops.stream), "simrank_query_pairs")
-                    self._d2h(got, val_dev, 8 * mine.size)
-                    self._sync()
+                    ops.d2h(got, val_dev)
+                    ops.synchronize()
                 finally:
                     ops._free(cols_dev)
                     if rows_dev != a_dev:
@@ -299,8 +256,8 @@ class Reader:
         n_q, k = int(node_ids.size), check_k(k)
         if n_q == 0:
             return np.empty((0, k), dtype=np.int32), np.empty((0, k), dtype=np.float64)
-        pos_dev = self._upload_i32(self.inv[node_ids])
-        ids_dev = self._upload_i32(node_ids)
+        pos_dev = ops.put(self.inv[node_ids])
+        ids_dev = ops.put(node_ids)
         pieces = []
         try:
             for b in self.blocks:
@@ -313,9 +270,9 @@ class Reader:
                     check(self.q.simrank_query_topk(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev,
                                                     ids_dev, n_q, b["col_ids"], kk, idx_dev, val_dev, ops.stream),
                           "simrank_query_topk")
-                    self._d2h(idx, idx_dev, 4 * n_q * kk)
-                    self._d2h(val, val_dev, 8 * n_q * kk)
-                    self._sync()
+                    ops.d2h(idx, idx_dev)
+                    ops.d2h(val, val_dev)
+                    ops.synchronize()
                 finally:
                     ops._free(idx_dev)
                     ops._free(val_dev)
@@ -327,15 +284,3 @@ class Reader:
             return pieces[0]
         return merge_topk(pieces, k)
 
-
-def _timed(ops, launch) -> float:
-    a, b = ops.event(), ops.event()
-    try:
-        ops.record(a)
-        launch()
-        ops.record(b)
-        ops.event_synchronize(b)
-        return ops.elapsed_ms(a, b)
-    finally:
-        ops.event_destroy(a)
-        ops.event_destroy(b)

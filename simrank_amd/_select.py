@@ -9,14 +9,10 @@ from __future__ import annotations
 import ctypes as C
 import math
 import numbers
-import os
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libsimrank_select.so")
-HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "simrank_select.h")
+from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, Companion  # noqa: F401 (the layouts a block may have)
 
 VERSION = 1              # SIMRANK_SELECT_VERSION of include/simrank_select.h
-PANEL_F32, ROWMAJOR_F32, PANEL_F16 = 0, 1, 2
 
 _vp, _i64, _i32, _f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 
@@ -37,29 +33,8 @@ class SelectError(RuntimeError):
     """A call into libsimrank_select.so failed."""
 
 
-_lib = None
-
-
-def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise SelectError(f"{LIB_PATH} is missing: build it with `make -C simrank_amd/csrc` (no CPU fallback)")
-        lib = C.CDLL(LIB_PATH)
-        for name, argtypes in PROTOTYPES.items():
-            fn = getattr(lib, name)
-            fn.argtypes = argtypes
-            fn.restype = _RESTYPES.get(name, C.c_int)
-        if lib.simrank_select_version() != VERSION:
-            raise SelectError(f"libsimrank_select.so version {lib.simrank_select_version()} != {VERSION}")
-        _lib = lib
-    return _lib
-
-
-def check(rc: int, what: str):
-    if rc != 0:
-        msg = load().simrank_select_last_error().decode(errors="replace")
-        raise SelectError(f"{what} failed ({rc}): {msg}")
+_c = Companion("select", VERSION, PROTOTYPES, _RESTYPES, SelectError)
+LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.check
 
 
 def check_threshold(t, max_pairs=None):

@@ -18,6 +18,7 @@ import numpy as np
 from . import _f64, hostpool
 from ._query import SolverQueries
 from ._f64 import F64MemoryError, check
+from .driver import prior_matrix
 
 
 def refusal(world, specs, mode, ops_factory) -> str | None:
@@ -33,17 +34,6 @@ def refusal(world, specs, mode, ops_factory) -> str | None:
     if any(s.dense_terms != 3 for s in specs):
         return "storage_precision='f64' computes exact float64 products: dense_precision must be 'f32'"
     return None
-
-
-def _prior64(spec):
-    """The prior as SimRank.py:453 blends it: float64, C-contiguous, n x n (NumPy's broadcast error otherwise)."""
-    if spec.apriori is None:
-        return None
-    a = np.asarray(spec.apriori)
-    n = spec.csr.n_rows
-    if a.shape != (n, n):
-        raise ValueError(f"operands could not be broadcast together with shapes ({n},{n}) {a.shape} ")
-    return np.ascontiguousarray(a, dtype=np.float64)
 
 
 class F64Plan:
@@ -172,7 +162,7 @@ class F64Solver(SolverQueries):
         self.broadcast_error = None
         self.plan = None
         self._counts = {}                        # id(csr) -> (csr, u8 Matrix): what gates the updates
-        priors = [_prior64(s) for s in specs]
+        priors = [prior_matrix(s, np.float64) for s in specs]
         if self.bipartite:
             a, b = specs
             strict = a.evidence_from is not None and b.evidence_from is a.csr       # quirk Q2: Evidence_N1 on both

@@ -8,16 +8,17 @@ count of update k is read on small graphs, and a banded hand-back (csrc/handback
 upper-triangle form is opt-in, ``SIMRANK_SYM_HANDBACK=1``, and checks on the device that the result is symmetric).
 
 An asymmetric prior (``SimRank.py:453``: asymmetric iterates) runs in the same plans with leg 2 stored transposed and the
-epilogue as a pass of its own.  ``driver.Solver`` (the same choreography in Python) stays for what a plan does not run: the
-dense / hybrid GEMM modes, virtual or real ranks (``LocalWorld(P > 1)``, ``TorchWorld``), non-default
-kernel knobs, and the NumPy test double of the CPU tests.
+epilogue as a pass of its own.  Several ranks, virtual or real (``LocalWorld(P > 1)``, ``TorchWorld``), run in
+``cshard.CShardSolver``.  The same choreography kernel by kernel in Python — the dense / hybrid GEMM modes, non-default
+kernel knobs, the NumPy test double of the CPU tests — is ``tests/pydriver.py``, a test double that plugs in through
+``estimators.PYTHON_SOLVER``.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from ._query import SolverQueries
-from .driver import LocalWorld, lean_knobs
+from .driver import LocalWorld, lean_knobs, prior_matrix
 
 
 def applies(ops_factory, world, specs, mode) -> bool:
@@ -51,20 +52,8 @@ def applies(ops_factory, world, specs, mode) -> bool:
     return True
 
 
-def _prior32(spec):
-    """The prior as the plans take it: float32, C-contiguous (SimRank.py:453 blends a float64 array; the rounding to
-    float32 is the engine's storage precision, as in driver.Side)."""
-    if spec.apriori is None:
-        return None
-    a = np.asarray(spec.apriori)
-    n = spec.csr.n_rows
-    if a.shape != (n, n):
-        raise ValueError(f"operands could not be broadcast together with shapes ({n},{n}) {a.shape} ")
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
 class PlanSolver(SolverQueries):
-    """``driver.Solver``'s surface over ``engine.Plan`` / ``engine.BiPlan``."""
+    """The solver surface ``estimators.py`` asks for, over ``engine.Plan`` / ``engine.BiPlan``."""
 
     mode = "sparse"
 
@@ -89,12 +78,12 @@ class PlanSolver(SolverQueries):
                     f"operands could not be broadcast together with shapes "
                     f"({self.n[0]},{self.n[0]}) ({self.n[1]},{self.n[1]}) ")
             self.plan = BiPlan(ops, a.csr, a.rowscale, b.rowscale, c1=a.coef, c2=b.coef, evidence=evidence,
-                               apriori1=_prior32(a), apriori2=_prior32(b), lbd1=a.lbd, lbd2=b.lbd,
+                               apriori1=prior_matrix(a, np.float32), apriori2=prior_matrix(b, np.float32), lbd1=a.lbd, lbd2=b.lbd,
                                strict_reference=strict)
         else:
             (s,) = specs
             self.n = [s.csr.n_rows]
-            ap = _prior32(s)
+            ap = prior_matrix(s, np.float32)
             if ap is not None and s.storage == "fp16" and not (np.isfinite(ap).all() and float(np.abs(ap).max()) < 3.99):
                 raise ValueError("storage_precision='fp16' needs prior values below 4 in magnitude")
             self.plan = Plan(ops, s.csr, s.rowscale, coef=s.coef, evidence=s.evidence_from is not None, apriori=ap,

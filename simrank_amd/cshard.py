@@ -13,7 +13,7 @@ panels themselves on the links).  ``CShardSolver`` gives that loop the few metho
 Since round 5 the same solver runs the f32 (parity-grade) sharded fits of an RCCL world as well — every class with
 class, the two-matrix ones through ``simrank_shardbiplan_*``, asymmetric priors with a second all-to-all and an un-fused
 epilogue — so that what a multi-GPU user's ``fit`` runs is the C loop, not a second choreography in Python;
-``driver.Solver`` keeps the GEMM modes and the CPU rehearsal over gloo with the NumPy test double.
+the Python choreography of ``tests/pydriver.py`` (a test double) keeps the GEMM modes and the CPU rehearsal over gloo.
 """
 from __future__ import annotations
 
@@ -22,7 +22,7 @@ import os
 import numpy as np
 
 from ._query import SolverQueries
-from .driver import LocalWorld, TorchWorld
+from .driver import LocalWorld, TorchWorld, prior_matrix
 
 
 def applies(world, specs, mode) -> str | None:
@@ -88,16 +88,6 @@ def _rccl_comm(world, ops):
     return comm
 
 
-def _prior32(spec):
-    if spec.apriori is None:
-        return None
-    a = np.asarray(spec.apriori)
-    n = spec.csr.n_rows
-    if a.shape != (n, n):
-        raise ValueError(f"operands could not be broadcast together with shapes ({n},{n}) {a.shape} ")
-    return np.ascontiguousarray(a, dtype=np.float32)
-
-
 class CShardSolver(SolverQueries):
     """The estimators' view of ``engine.ShardPlans`` / ``engine.ShardBiPlans``: the sharded loops behind the C ABI
     (csrc/shardplan.hip) — every class, f32 (the parity path) or, for SimRank / SimRank++ without a prior, fp16-held
@@ -140,14 +130,14 @@ class CShardSolver(SolverQueries):
             if form == 1 and not (fits(self.n[0]) or fits(self.n[1])):
                 form = 0
             self.plans = ShardBiPlans(ops, a.csr, a.rowscale, b.rowscale, c1=a.coef, c2=b.coef, evidence=evidence,
-                                      apriori1=_prior32(a), apriori2=_prior32(b), lbd1=a.lbd, lbd2=b.lbd,
+                                      apriori1=prior_matrix(a, np.float32), apriori2=prior_matrix(b, np.float32), lbd1=a.lbd, lbd2=b.lbd,
                                       strict_reference=strict, leg2_form=form, **common)
         else:
             (s,) = specs
             if form == 1 and s.csr.n_rows % (32 * world.size):
                 form = 0
             self.plans = ShardPlans(ops, s.csr, rowscale=s.rowscale, coef=s.coef, evidence=s.evidence_from is not None,
-                                    apriori=_prior32(s), lbd=s.lbd, storage=self.storage, leg2_form=form, **common)
+                                    apriori=prior_matrix(s, np.float32), lbd=s.lbd, storage=self.storage, leg2_form=form, **common)
         self.root = local or world.rank == 0
 
     def run(self, iterations, eps, on_iteration=None, on_converged=None):

@@ -11,11 +11,8 @@
 // Tiles go panel-major (consecutive tiles share a 16-column panel of the gathered matrix, whose N x 128 bytes stay
 // L2-resident) and are dealt to the eight XCDs in contiguous runs (workgroup w runs on XCD w % 8).  The gathers go
 // in CSR order with one accumulator, so every element's sum has one fixed order: two runs give the same bits.
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -23,41 +20,14 @@
 
 #include "simrank_f64.h"
 
+#define COMPANION_ERR_INVALID SIMRANK_F64_ERR_INVALID
+#define COMPANION_ERR_HIP SIMRANK_F64_ERR_HIP
+#include "companion.h"
+
 namespace {
-
-thread_local std::string g_error;
-
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_error = buf;
-}
-
-#define F64_REQUIRE(cond, ...)            \
-    do {                                  \
-        if (!(cond)) {                    \
-            set_error(__VA_ARGS__);       \
-            return SIMRANK_F64_ERR_INVALID; \
-        }                                 \
-    } while (0)
-
-#define F64_HIP(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_));                      \
-            (void)hipGetLastError();                                                       \
-            return SIMRANK_F64_ERR_HIP;                                                    \
-        }                                                                                  \
-    } while (0)
 
 constexpr int kTile = 16;
 constexpr int kSlots = 1024;              // convergence counters, spread so that tiles seldom meet on one address
-
-inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 // row pitch in doubles: whole 128-byte lines, and never a large power of two (a panel's lines would share channels)
 int64_t pitch(int64_t n) {
@@ -396,27 +366,27 @@ int64_t t_elems(const simrank_f64_side* sides, int32_t n_sides) {
 }
 
 int check_sides(const simrank_f64_side* sides, int32_t n_sides) {
-    F64_REQUIRE(sides, "sides is NULL");
-    F64_REQUIRE(n_sides == 1 || n_sides == 2, "n_sides must be 1 or 2 (got %d)", (int)n_sides);
+    REQUIRE(sides, "sides is NULL");
+    REQUIRE(n_sides == 1 || n_sides == 2, "n_sides must be 1 or 2 (got %d)", (int)n_sides);
     for (int32_t u = 0; u < n_sides; ++u) {
         const simrank_f64_side& s = sides[u];
-        F64_REQUIRE(s.n_rows > 0 && s.n_cols > 0 && s.n_rows < (int64_t(1) << 31) && s.n_cols < (int64_t(1) << 31),
+        REQUIRE(s.n_rows > 0 && s.n_cols > 0 && s.n_rows < (int64_t(1) << 31) && s.n_cols < (int64_t(1) << 31),
                     "side %d: bad shape %lld x %lld", (int)u, (long long)s.n_rows, (long long)s.n_cols);
-        F64_REQUIRE(s.nnz >= 0 && s.nnz < (int64_t(1) << 31), "side %d: bad nnz %lld", (int)u, (long long)s.nnz);
-        F64_REQUIRE(s.rowptr && s.rowscale && (s.col || s.nnz == 0), "side %d: rowptr, col or rowscale is NULL", (int)u);
-        F64_REQUIRE(s.rowptr[0] == 0 && s.rowptr[s.n_rows] == s.nnz, "side %d: rowptr does not run from 0 to nnz", (int)u);
+        REQUIRE(s.nnz >= 0 && s.nnz < (int64_t(1) << 31), "side %d: bad nnz %lld", (int)u, (long long)s.nnz);
+        REQUIRE(s.rowptr && s.rowscale && (s.col || s.nnz == 0), "side %d: rowptr, col or rowscale is NULL", (int)u);
+        REQUIRE(s.rowptr[0] == 0 && s.rowptr[s.n_rows] == s.nnz, "side %d: rowptr does not run from 0 to nnz", (int)u);
         for (int64_t r = 0; r < s.n_rows; ++r)
-            F64_REQUIRE(s.rowptr[r + 1] >= s.rowptr[r], "side %d: rowptr decreases at row %lld", (int)u, (long long)r);
+            REQUIRE(s.rowptr[r + 1] >= s.rowptr[r], "side %d: rowptr decreases at row %lld", (int)u, (long long)r);
         for (int64_t p = 0; p < s.nnz; ++p)
-            F64_REQUIRE(s.col[p] >= 0 && s.col[p] < s.n_cols, "side %d: column %d out of range at %lld", (int)u,
+            REQUIRE(s.col[p] >= 0 && s.col[p] < s.n_cols, "side %d: column %d out of range at %lld", (int)u,
                         (int)s.col[p], (long long)p);
-        F64_REQUIRE(!s.counts || ((s.counts_n == s.n_rows || s.counts_n == 1) && s.counts_ld >= s.counts_n),
+        REQUIRE(!s.counts || ((s.counts_n == s.n_rows || s.counts_n == 1) && s.counts_ld >= s.counts_n),
                     "side %d: counts must be n x n or 1 x 1 with ld >= n", (int)u);
     }
     if (n_sides == 1)
-        F64_REQUIRE(sides[0].n_rows == sides[0].n_cols, "one side needs a square pattern");
+        REQUIRE(sides[0].n_rows == sides[0].n_cols, "one side needs a square pattern");
     else
-        F64_REQUIRE(sides[1].n_rows == sides[0].n_cols && sides[1].n_cols == sides[0].n_rows &&
+        REQUIRE(sides[1].n_rows == sides[0].n_cols && sides[1].n_cols == sides[0].n_rows &&
                         sides[1].nnz == sides[0].nnz, "side 1's pattern must be the transpose of side 0's");
     return SIMRANK_F64_OK;
 }
@@ -467,7 +437,7 @@ void free_plan(simrank_f64_plan* p) {
 
 template <class T>
 int dmalloc(T** ptr, int64_t count) {
-    F64_HIP(hipMalloc(reinterpret_cast<void**>(ptr), size_t(std::max<int64_t>(count, 1)) * sizeof(T)));
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(ptr), size_t(std::max<int64_t>(count, 1)) * sizeof(T)));
     return SIMRANK_F64_OK;
 }
 
@@ -477,7 +447,7 @@ int launch_identity(double* X, int64_t ld, int64_t n, hipStream_t st) {
     const int64_t total = n * ld;
     const int grid = (int)std::min<int64_t>((total + 255) / 256, 4096);
     hipLaunchKernelGGL(identity_kernel, dim3(grid), dim3(256), 0, st, X, ld, n);
-    F64_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_F64_OK;
 }
 
@@ -492,12 +462,12 @@ int update(simrank_f64_plan* p, int u, double eps) {
     const int64_t nrb = (n_w + kTile - 1) / kTile, npa = (n_y + kTile - 1) / kTile;
     unsigned long long* slots = p->slots + u * kSlots;
     const bool t = p->timing;
-    if (t) F64_HIP(hipEventRecord(p->ev[0], p->stream));
+    if (t) HIP_CHECK(hipEventRecord(p->ev[0], p->stream));
     const int64_t ta = nrb * npa;
     hipLaunchKernelGGL(leg_a_kernel, dim3(tiles_grid(ta)), dim3(256), 0, p->stream, s.rowptr, s.col, s.rs, Y, y.ld,
                        n_w, n_y, p->T, ldt, nrb, ta);
-    F64_HIP(hipGetLastError());
-    if (t) F64_HIP(hipEventRecord(p->ev[1], p->stream));
+    HIP_CHECK(hipGetLastError());
+    if (t) HIP_CHECK(hipEventRecord(p->ev[1], p->stream));
     Epi e{s.coef, s.lbd, eps, s.counts, s.cld, s.cn, s.prior, s.ld};
     const int64_t tb = nrb * nrb;
     if (p->sym)
@@ -506,21 +476,21 @@ int update(simrank_f64_plan* p, int u, double eps) {
     else
         hipLaunchKernelGGL(leg_b_kernel<false>, dim3(tiles_grid(tb)), dim3(256), 0, p->stream, s.rowptr, s.col,
                            s.rs, p->T, ldt, n_w, e, Sold, X, nrb, tb, slots);
-    F64_HIP(hipGetLastError());
-    if (t) F64_HIP(hipEventRecord(p->ev[2], p->stream));
+    HIP_CHECK(hipGetLastError());
+    if (t) HIP_CHECK(hipEventRecord(p->ev[2], p->stream));
     if (p->sym)
         hipLaunchKernelGGL(mirror_kernel, dim3(tiles_grid(tb)), dim3(256), 0, p->stream, X, s.ld, n_w, nrb);
     else
         hipLaunchKernelGGL(transpose_epilogue_kernel, dim3(tiles_grid(tb)), dim3(256), 0, p->stream, X, Sold, n_w, e, nrb,
                            slots);
-    F64_HIP(hipGetLastError());
-    if (t) F64_HIP(hipEventRecord(p->ev[3], p->stream));
+    HIP_CHECK(hipGetLastError());
+    if (t) HIP_CHECK(hipEventRecord(p->ev[3], p->stream));
     s.cur ^= 1;
     if (t) {
-        F64_HIP(hipEventSynchronize(p->ev[3]));
+        HIP_CHECK(hipEventSynchronize(p->ev[3]));
         for (int q = 0; q < 3; ++q) {
             float ms = 0.f;
-            F64_HIP(hipEventElapsedTime(&ms, p->ev[q], p->ev[q + 1]));
+            HIP_CHECK(hipEventElapsedTime(&ms, p->ev[q], p->ev[q + 1]));
             p->ms[q] += ms;
         }
     }
@@ -528,9 +498,9 @@ int update(simrank_f64_plan* p, int u, double eps) {
 }
 
 int side_ok(simrank_f64_plan* p, int32_t side) {
-    F64_REQUIRE(p, "plan is NULL");
-    F64_REQUIRE(side >= 0 && side < p->ns, "side %d out of range (the plan has %d)", (int)side, (int)p->ns);
-    F64_REQUIRE(!p->released, "the plan's matrices were released (simrank_f64_plan_trim)");
+    REQUIRE(p, "plan is NULL");
+    REQUIRE(side >= 0 && side < p->ns, "side %d out of range (the plan has %d)", (int)side, (int)p->ns);
+    REQUIRE(!p->released, "the plan's matrices were released (simrank_f64_plan_trim)");
     return SIMRANK_F64_OK;
 }
 
@@ -545,7 +515,7 @@ int simrank_f64_version(void) { return SIMRANK_F64_VERSION; }
 const char* simrank_f64_last_error(void) { return g_error.c_str(); }
 
 int simrank_f64_plan_bytes(const simrank_f64_side* sides, int32_t n_sides, int64_t* bytes) {
-    F64_REQUIRE(bytes, "bytes is NULL");
+    REQUIRE(bytes, "bytes is NULL");
     const int rc = check_sides(sides, n_sides);
     if (rc) return rc;
     int64_t b = 8 * t_elems(sides, n_sides) + 8 * 2 * kSlots;
@@ -555,9 +525,9 @@ int simrank_f64_plan_bytes(const simrank_f64_side* sides, int32_t n_sides, int64
 }
 
 int simrank_f64_mem_info(int64_t* free_bytes, int64_t* total_bytes) {
-    F64_REQUIRE(free_bytes && total_bytes, "NULL argument");
+    REQUIRE(free_bytes && total_bytes, "NULL argument");
     size_t f = 0, t = 0;
-    F64_HIP(hipMemGetInfo(&f, &t));
+    HIP_CHECK(hipMemGetInfo(&f, &t));
     *free_bytes = (int64_t)f;
     *total_bytes = (int64_t)t;
     return SIMRANK_F64_OK;
@@ -565,13 +535,13 @@ int simrank_f64_mem_info(int64_t* free_bytes, int64_t* total_bytes) {
 
 int simrank_f64_plan_create(const simrank_f64_side* sides, int32_t n_sides, const simrank_f64_options* options,
                             void* stream, simrank_f64_plan** out) {
-    F64_REQUIRE(out, "out is NULL");
+    REQUIRE(out, "out is NULL");
     *out = nullptr;
     int64_t need = 0;
     int rc = simrank_f64_plan_bytes(sides, n_sides, &need);
     if (rc) return rc;
     size_t f = 0, tot = 0;
-    F64_HIP(hipMemGetInfo(&f, &tot));
+    HIP_CHECK(hipMemGetInfo(&f, &tot));
     if (need > (int64_t)f) {
         set_error("storage_precision='f64' needs %.2f GiB of device memory for its matrices; %.2f GiB of %.2f GiB are free",
                   need / 1073741824.0, f / 1073741824.0, tot / 1073741824.0);
@@ -644,29 +614,29 @@ int simrank_f64_plan_destroy(simrank_f64_plan* p) {
 }
 
 int simrank_f64_plan_reset(simrank_f64_plan* p) {
-    F64_REQUIRE(p, "plan is NULL");
-    F64_REQUIRE(!p->released, "the plan's matrices were released (simrank_f64_plan_trim)");
+    REQUIRE(p, "plan is NULL");
+    REQUIRE(!p->released, "the plan's matrices were released (simrank_f64_plan_trim)");
     for (int32_t u = 0; u < p->ns; ++u) {
         Side& s = p->s[u];
         s.cur = 0;
         const int rc = launch_identity(s.S[0], s.ld, s.n, p->stream);
         if (rc) return rc;
     }
-    F64_HIP(hipStreamSynchronize(p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
     return SIMRANK_F64_OK;
 }
 
 int simrank_f64_plan_step(simrank_f64_plan* p, double eps, int64_t* changed) {
-    F64_REQUIRE(p && changed, "NULL argument");
-    F64_REQUIRE(!p->released, "the plan's matrices were released (simrank_f64_plan_trim)");
-    F64_HIP(hipMemsetAsync(p->slots, 0, sizeof(unsigned long long) * 2 * kSlots, p->stream));
+    REQUIRE(p && changed, "NULL argument");
+    REQUIRE(!p->released, "the plan's matrices were released (simrank_f64_plan_trim)");
+    HIP_CHECK(hipMemsetAsync(p->slots, 0, sizeof(unsigned long long) * 2 * kSlots, p->stream));
     for (int32_t u = 0; u < p->ns; ++u) {
         const int rc = update(p, u, eps);
         if (rc) return rc;
     }
     std::vector<unsigned long long> h(2 * kSlots);
-    F64_HIP(hipMemcpyAsync(h.data(), p->slots, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, p->stream));
-    F64_HIP(hipStreamSynchronize(p->stream));
+    HIP_CHECK(hipMemcpyAsync(h.data(), p->slots, h.size() * sizeof(h[0]), hipMemcpyDeviceToHost, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
     for (int32_t u = 0; u < p->ns; ++u) {
         unsigned long long c = 0;
         for (int q = 0; q < kSlots; ++q) c += h[u * kSlots + q];
@@ -677,7 +647,7 @@ int simrank_f64_plan_step(simrank_f64_plan* p, double eps, int64_t* changed) {
 }
 
 int simrank_f64_plan_set_timing(simrank_f64_plan* p, int32_t on) {
-    F64_REQUIRE(p, "plan is NULL");
+    REQUIRE(p, "plan is NULL");
     p->timing = on != 0;
     p->ms[0] = p->ms[1] = p->ms[2] = 0;
     p->steps = 0;
@@ -685,7 +655,7 @@ int simrank_f64_plan_set_timing(simrank_f64_plan* p, int32_t on) {
 }
 
 int simrank_f64_plan_leg_times(simrank_f64_plan* p, double* ms, int32_t* steps) {
-    F64_REQUIRE(p && ms && steps, "NULL argument");
+    REQUIRE(p && ms && steps, "NULL argument");
     for (int q = 0; q < 3; ++q) ms[q] = p->ms[q];
     *steps = p->steps;
     return SIMRANK_F64_OK;
@@ -695,10 +665,10 @@ int simrank_f64_plan_result(simrank_f64_plan* p, int32_t side, double* dst, int6
     int rc = side_ok(p, side);
     if (rc) return rc;
     const Side& s = p->s[side];
-    F64_REQUIRE(dst && ld >= s.n, "bad result arguments (dst NULL or ld < %lld)", (long long)s.n);
-    F64_HIP(hipMemcpy2DAsync(dst, size_t(ld) * 8, s.S[s.cur], size_t(s.ld) * 8, size_t(s.n) * 8, size_t(s.n),
+    REQUIRE(dst && ld >= s.n, "bad result arguments (dst NULL or ld < %lld)", (long long)s.n);
+    HIP_CHECK(hipMemcpy2DAsync(dst, size_t(ld) * 8, s.S[s.cur], size_t(s.ld) * 8, size_t(s.n) * 8, size_t(s.n),
                              hipMemcpyDeviceToHost, p->stream));
-    F64_HIP(hipStreamSynchronize(p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
     return SIMRANK_F64_OK;
 }
 
@@ -707,8 +677,8 @@ int simrank_f64_plan_topk(simrank_f64_plan* p, int32_t side, int32_t k, int32_t 
     int rc = side_ok(p, side);
     if (rc) return rc;
     const Side& s = p->s[side];
-    F64_REQUIRE(idx_host && val_host, "idx_host or val_host is NULL");
-    F64_REQUIRE(k >= 1 && k <= s.n, "k must be in [1, %lld] (got %d)", (long long)s.n, (int)k);
+    REQUIRE(idx_host && val_host, "idx_host or val_host is NULL");
+    REQUIRE(k >= 1 && k <= s.n, "k must be in [1, %lld] (got %d)", (long long)s.n, (int)k);
     int32_t* idx = nullptr;
     double* val = nullptr;
     if ((rc = dmalloc(&idx, s.n * k)) || (rc = dmalloc(&val, s.n * k))) {
@@ -745,8 +715,8 @@ int simrank_f64_plan_topk(simrank_f64_plan* p, int32_t side, int32_t k, int32_t 
 int simrank_f64_plan_count_above(simrank_f64_plan* p, int32_t side, double t, int64_t* offsets_host) {
     int rc = side_ok(p, side);
     if (rc) return rc;
-    F64_REQUIRE(offsets_host, "offsets_host is NULL");
-    F64_REQUIRE(std::isfinite(t) && t > 0.0, "the threshold must be a finite number > 0 (got %g)", t);
+    REQUIRE(offsets_host, "offsets_host is NULL");
+    REQUIRE(std::isfinite(t) && t > 0.0, "the threshold must be a finite number > 0 (got %g)", t);
     const Side& s = p->s[side];
     (void)hipFree(p->sel_off);
     p->sel_off = nullptr;
@@ -768,8 +738,8 @@ int simrank_f64_plan_count_above(simrank_f64_plan* p, int32_t side, double t, in
     offsets_host[0] = 0;
     for (int64_t r = 0; r < s.n; ++r) offsets_host[r + 1] = offsets_host[r] + h[(size_t)r];
     if ((rc = dmalloc(&p->sel_off, s.n + 1))) return rc;
-    F64_HIP(hipMemcpyAsync(p->sel_off, offsets_host, size_t(s.n + 1) * 8, hipMemcpyHostToDevice, p->stream));
-    F64_HIP(hipStreamSynchronize(p->stream));
+    HIP_CHECK(hipMemcpyAsync(p->sel_off, offsets_host, size_t(s.n + 1) * 8, hipMemcpyHostToDevice, p->stream));
+    HIP_CHECK(hipStreamSynchronize(p->stream));
     p->sel_side = side;
     p->sel_t = t;
     p->sel_n = offsets_host[s.n];
@@ -780,10 +750,10 @@ int simrank_f64_plan_emit_above(simrank_f64_plan* p, int32_t side, double t, int
                                 double* vals_host) {
     int rc = side_ok(p, side);
     if (rc) return rc;
-    F64_REQUIRE(p->sel_side == side && p->sel_t == t && p->sel_off,
+    REQUIRE(p->sel_side == side && p->sel_t == t && p->sel_off,
                 "simrank_f64_plan_emit_above needs simrank_f64_plan_count_above of the same side and threshold first");
-    F64_REQUIRE(total == p->sel_n, "total %lld is not the count's %lld", (long long)total, (long long)p->sel_n);
-    F64_REQUIRE(total == 0 || (ids_host && vals_host), "ids_host or vals_host is NULL");
+    REQUIRE(total == p->sel_n, "total %lld is not the count's %lld", (long long)total, (long long)p->sel_n);
+    REQUIRE(total == 0 || (ids_host && vals_host), "ids_host or vals_host is NULL");
     if (total == 0) return SIMRANK_F64_OK;
     const Side& s = p->s[side];
     int32_t* ids = nullptr;
@@ -809,7 +779,7 @@ int simrank_f64_plan_emit_above(simrank_f64_plan* p, int32_t side, double t, int
 }
 
 int simrank_f64_plan_trim(simrank_f64_plan* p) {
-    F64_REQUIRE(p, "plan is NULL");
+    REQUIRE(p, "plan is NULL");
     (void)hipStreamSynchronize(p->stream);
     free_plan(p);
     p->released = true;
@@ -817,13 +787,13 @@ int simrank_f64_plan_trim(simrank_f64_plan* p) {
 }
 
 int simrank_f64_plan_get(const simrank_f64_plan* p, int32_t side, const char* key, int64_t* value) {
-    F64_REQUIRE(p && key && value, "plan, key or value is NULL");
-    F64_REQUIRE(side >= 0 && side < p->ns, "side %d out of range (the plan has %d)", (int)side, (int)p->ns);
+    REQUIRE(p && key && value, "plan, key or value is NULL");
+    REQUIRE(side >= 0 && side < p->ns, "side %d out of range (the plan has %d)", (int)side, (int)p->ns);
     const Side& s = p->s[side];
     if (!std::strcmp(key, "iterate")) *value = p->released ? 0 : (int64_t)(uintptr_t)s.S[s.cur];
     else if (!std::strcmp(key, "iterate_ld")) *value = s.ld;
     else if (!std::strcmp(key, "iterate_rows")) *value = s.n;
-    else F64_REQUIRE(false, "unknown key '%s'", key);
+    else REQUIRE(false, "unknown key '%s'", key);
     return SIMRANK_F64_OK;
 }
 

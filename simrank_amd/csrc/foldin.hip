@@ -17,47 +17,22 @@
 //             workgroup of 32 half waves per row, 32 strided partial sums added in a fixed order.  No floating-point atomics anywhere:
 //             the same call gives the same bits twice.  The epilogue is float64 (scale, coefficient, evidence by ldexp,
 //             prior blend).
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-
-#include <cstdarg>
 #include <cstdio>
 #include <string>
 
 #include "simrank_foldin.h"
 
+#define COMPANION_ERR_INVALID SIMRANK_FOLDIN_ERR_INVALID
+#define COMPANION_ERR_HIP SIMRANK_FOLDIN_ERR_HIP
+#include "companion.h"
+
 namespace {
 
-thread_local std::string g_error;
+COMPANION_SAME_LAYOUT(SIMRANK_FOLDIN_, PANEL_F32);
+COMPANION_SAME_LAYOUT(SIMRANK_FOLDIN_, ROWMAJOR_F32);
+COMPANION_SAME_LAYOUT(SIMRANK_FOLDIN_, PANEL_F16);
+COMPANION_SAME_LAYOUT(SIMRANK_FOLDIN_, ROWMAJOR_F64);
 
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_error = buf;
-}
-
-#define FLD_REQUIRE(cond, ...)                 \
-    do {                                       \
-        if (!(cond)) {                         \
-            set_error(__VA_ARGS__);            \
-            return SIMRANK_FOLDIN_ERR_INVALID; \
-        }                                      \
-    } while (0)
-
-#define FLD_HIP(call)                                                 \
-    do {                                                              \
-        hipError_t e_ = (call);                                       \
-        if (e_ != hipSuccess) {                                       \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_)); \
-            (void)hipGetLastError();                                  \
-            return SIMRANK_FOLDIN_ERR_HIP;                            \
-        }                                                             \
-    } while (0)
-
-constexpr float kHalfScale = 1.0f / 16384.0f;          // fp16-held values are value x 2^14
 constexpr int kTile = SIMRANK_FOLDIN_TILE;
 constexpr int kLongRow = SIMRANK_FOLDIN_LONG_ROW;
 static_assert(kTile == 32, "a tile is half a wave and one member word");
@@ -354,38 +329,38 @@ int64_t simrank_foldin_t_bytes(int32_t layout, int64_t n_src) {
 }
 
 int simrank_foldin_alloc(void** ptr, size_t bytes) {
-    FLD_REQUIRE(ptr, "ptr is NULL");
+    REQUIRE(ptr, "ptr is NULL");
     *ptr = nullptr;
     if (bytes == 0) return SIMRANK_FOLDIN_OK;
-    FLD_HIP(hipMalloc(ptr, bytes));
+    HIP_CHECK(hipMalloc(ptr, bytes));
     return SIMRANK_FOLDIN_OK;
 }
 
 int simrank_foldin_free(void* ptr) {
-    if (ptr) FLD_HIP(hipFree(ptr));
+    if (ptr) HIP_CHECK(hipFree(ptr));
     return SIMRANK_FOLDIN_OK;
 }
 
 int simrank_foldin_gather(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols,
                           const int32_t* col_ids, int64_t col_base, const int32_t* list_ptr, const int32_t* list_pos,
                           const double* w, int32_t n_tile, void* T, int64_t n_src, void* stream) {
-    FLD_REQUIRE(known(layout), "unknown layout %d", (int)layout);
-    FLD_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
+    REQUIRE(known(layout), "unknown layout %d", (int)layout);
+    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
                 "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    FLD_REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), "bad number of source nodes %lld", (long long)n_src);
-    FLD_REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
+    REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), "bad number of source nodes %lld", (long long)n_src);
+    REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
     const bool panels = layout == SIMRANK_FOLDIN_PANEL_F32 || layout == SIMRANK_FOLDIN_PANEL_F16;
-    FLD_REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
+    REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
                 panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
-    FLD_REQUIRE(col_ids || (col_base >= 0 && col_base + n_cols <= n_src), "columns %lld .. %lld are not source nodes",
+    REQUIRE(col_ids || (col_base >= 0 && col_base + n_cols <= n_src), "columns %lld .. %lld are not source nodes",
                 (long long)col_base, (long long)(col_base + n_cols));
     if (n_cols == 0 || n_src == 0) return SIMRANK_FOLDIN_OK;
-    FLD_REQUIRE(S && T, "S or T is NULL");
-    FLD_REQUIRE(n_tile == 0 || (list_ptr && w), "list_ptr or w is NULL");
-    FLD_REQUIRE(reinterpret_cast<uintptr_t>(T) % 16 == 0, "T is not 16-byte aligned");
+    REQUIRE(S && T, "S or T is NULL");
+    REQUIRE(n_tile == 0 || (list_ptr && w), "list_ptr or w is NULL");
+    REQUIRE(reinterpret_cast<uintptr_t>(T) % 16 == 0, "T is not 16-byte aligned");
     const bool base16 = reinterpret_cast<uintptr_t>(S) % 16 == 0;
-    FLD_REQUIRE(base16 || !panels, "a panel block starts on 16 bytes");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    REQUIRE(base16 || !panels, "a panel block starts on 16 bytes");
+    hipStream_t st = as_stream(stream);
     switch (layout) {
         case SIMRANK_FOLDIN_PANEL_F32: {
             const unsigned grid = (unsigned)((n_cols + 255) / 256);
@@ -412,23 +387,23 @@ int simrank_foldin_gather(const void* S, int32_t layout, int64_t stride, int64_t
             break;
         }
     }
-    FLD_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_FOLDIN_OK;
 }
 
 int simrank_foldin_member(const int32_t* list_ptr, const int32_t* list_ids, const double* w, int32_t n_tile,
                           uint32_t* member, int64_t n_src, void* stream) {
-    FLD_REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), "bad number of source nodes %lld", (long long)n_src);
-    FLD_REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
+    REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), "bad number of source nodes %lld", (long long)n_src);
+    REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
     if (n_src == 0) return SIMRANK_FOLDIN_OK;
-    FLD_REQUIRE(member, "member is NULL");
-    FLD_REQUIRE(n_tile == 0 || (list_ptr && w), "list_ptr or w is NULL");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    FLD_HIP(hipMemsetAsync(member, 0, sizeof(uint32_t) * size_t(n_src), st));
+    REQUIRE(member, "member is NULL");
+    REQUIRE(n_tile == 0 || (list_ptr && w), "list_ptr or w is NULL");
+    hipStream_t st = as_stream(stream);
+    HIP_CHECK(hipMemsetAsync(member, 0, sizeof(uint32_t) * size_t(n_src), st));
     if (n_tile > 0) {
         hipLaunchKernelGGL(foldin_member_kernel, dim3((unsigned)n_tile), dim3(256), 0, st, list_ptr, list_ids, w, member,
                            n_src);
-        FLD_HIP(hipGetLastError());
+        HIP_CHECK(hipGetLastError());
     }
     return SIMRANK_FOLDIN_OK;
 }
@@ -437,16 +412,16 @@ int simrank_foldin_apply(const int32_t* rowptr, const int32_t* col, const double
                          const int32_t* long_rows, int64_t n_long, const void* T, int32_t t_layout, const uint32_t* member,
                          double coef, double lbd, const double* prior, int64_t ld_prior, int32_t n_tile, double* out,
                          int64_t ld_out, void* stream) {
-    FLD_REQUIRE(known(t_layout), "unknown layout %d", (int)t_layout);
-    FLD_REQUIRE(n_out >= 0 && n_out < (int64_t(1) << 31) && n_src >= 0 && n_src < (int64_t(1) << 31),
+    REQUIRE(known(t_layout), "unknown layout %d", (int)t_layout);
+    REQUIRE(n_out >= 0 && n_out < (int64_t(1) << 31) && n_src >= 0 && n_src < (int64_t(1) << 31),
                 "bad shape %lld x %lld", (long long)n_out, (long long)n_src);
-    FLD_REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
-    FLD_REQUIRE(n_long >= 0 && n_long <= n_out && (n_long == 0 || long_rows), "bad list of long rows");
-    FLD_REQUIRE(ld_out >= n_out && (!prior || ld_prior >= n_out), "a leading dimension is smaller than the %lld fitted nodes",
+    REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
+    REQUIRE(n_long >= 0 && n_long <= n_out && (n_long == 0 || long_rows), "bad list of long rows");
+    REQUIRE(ld_out >= n_out && (!prior || ld_prior >= n_out), "a leading dimension is smaller than the %lld fitted nodes",
                 (long long)n_out);
     if (n_out == 0 || n_tile == 0) return SIMRANK_FOLDIN_OK;
-    FLD_REQUIRE(rowptr && scale && out, "rowptr, scale or out is NULL");
-    FLD_REQUIRE(T && n_src > 0, "T is NULL or there are no source nodes");
+    REQUIRE(rowptr && scale && out, "rowptr, scale or out is NULL");
+    REQUIRE(T && n_src > 0, "T is NULL or there are no source nodes");
     Epilogue ep;
     ep.scale = scale;
     ep.prior = prior;
@@ -455,12 +430,12 @@ int simrank_foldin_apply(const int32_t* rowptr, const int32_t* col, const double
     ep.keep = 1.0 - lbd;
     ep.lbd = lbd;
     ep.evidence = member != nullptr;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = as_stream(stream);
     if (t_layout == SIMRANK_FOLDIN_ROWMAJOR_F64)
         launch_apply<double>(st, rowptr, col, n_out, n_src, long_rows, n_long, T, member, ep, n_tile, out, ld_out);
     else
         launch_apply<float>(st, rowptr, col, n_out, n_src, long_rows, n_long, T, member, ep, n_tile, out, ld_out);
-    FLD_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_FOLDIN_OK;
 }
 

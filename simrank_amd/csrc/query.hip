@@ -17,12 +17,8 @@
 //     topk    one wave per query row, k rounds of "largest element after the previous pick" in the total order (value
 //             descending, id ascending), the row's own node excluded by ID — the order and the empty-slot convention of
 //             the main library's top-k, on any subset of rows; the row is re-read from L2.
-#include <hip/hip_runtime.h>
-#include <hip/hip_fp16.h>
-
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -31,53 +27,16 @@
 
 #include "simrank_query.h"
 
+#define COMPANION_ERR_INVALID SIMRANK_QUERY_ERR_INVALID
+#define COMPANION_ERR_HIP SIMRANK_QUERY_ERR_HIP
+#include "companion.h"
+
 namespace {
 
-thread_local std::string g_error;
-
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_error = buf;
-}
-
-#define QRY_REQUIRE(cond, ...)                \
-    do {                                      \
-        if (!(cond)) {                        \
-            set_error(__VA_ARGS__);           \
-            return SIMRANK_QUERY_ERR_INVALID; \
-        }                                     \
-    } while (0)
-
-#define QRY_HIP(call)                                                 \
-    do {                                                              \
-        hipError_t e_ = (call);                                       \
-        if (e_ != hipSuccess) {                                       \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_)); \
-            (void)hipGetLastError();                                  \
-            return SIMRANK_QUERY_ERR_HIP;                             \
-        }                                                             \
-    } while (0)
-
-constexpr float kHalfScale = 1.0f / 16384.0f;          // fp16-held values are value x 2^14
-
-// element (r, c) of a block in layout L, widened as the dense hand-back widens it
-template <int L>
-__device__ inline double elem(const void* __restrict__ S, int64_t stride, int64_t r, int64_t c) {
-    if constexpr (L == SIMRANK_QUERY_PANEL_F32) {
-        return (double)static_cast<const float*>(S)[((c >> 5) * stride + r) * 32 + (c & 31)];
-    } else if constexpr (L == SIMRANK_QUERY_ROWMAJOR_F32) {
-        return (double)static_cast<const float*>(S)[r * stride + c];
-    } else if constexpr (L == SIMRANK_QUERY_PANEL_F16) {
-        const __half h = static_cast<const __half*>(S)[((c >> 6) * stride + r) * 64 + (c & 63)];
-        return (double)(__half2float(h) * kHalfScale);
-    } else {
-        return static_cast<const double*>(S)[r * stride + c];
-    }
-}
+COMPANION_SAME_LAYOUT(SIMRANK_QUERY_, PANEL_F32);
+COMPANION_SAME_LAYOUT(SIMRANK_QUERY_, ROWMAJOR_F32);
+COMPANION_SAME_LAYOUT(SIMRANK_QUERY_, PANEL_F16);
+COMPANION_SAME_LAYOUT(SIMRANK_QUERY_, ROWMAJOR_F64);
 
 constexpr int kRowsThreads = 256;
 constexpr int kRowsPerThread = 4;
@@ -175,12 +134,12 @@ __global__ __launch_bounds__(256) void query_topk_kernel(const void* __restrict_
 }
 
 int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols) {
-    QRY_REQUIRE(layout >= SIMRANK_QUERY_PANEL_F32 && layout <= SIMRANK_QUERY_ROWMAJOR_F64, "unknown layout %d", (int)layout);
-    QRY_REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
+    REQUIRE(layout >= SIMRANK_QUERY_PANEL_F32 && layout <= SIMRANK_QUERY_ROWMAJOR_F64, "unknown layout %d", (int)layout);
+    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
                 "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    QRY_REQUIRE(S || n_rows == 0 || n_cols == 0, "S is NULL");
+    REQUIRE(S || n_rows == 0 || n_cols == 0, "S is NULL");
     const bool panels = layout == SIMRANK_QUERY_PANEL_F32 || layout == SIMRANK_QUERY_PANEL_F16;
-    QRY_REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
+    REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
                 panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
     return SIMRANK_QUERY_OK;
 }
@@ -213,20 +172,20 @@ int simrank_query_rows(const void* S, int32_t layout, int64_t stride, int64_t n_
                        int64_t n_q, const int32_t* col_pos, int64_t n_out, double* out, int64_t ld_out, void* stream) {
     const int rc = check_block(S, layout, stride, n_rows, n_cols);
     if (rc) return rc;
-    QRY_REQUIRE(n_q >= 0 && n_out >= 0 && ld_out >= n_out, "bad output shape %lld x %lld (ld %lld)", (long long)n_q,
+    REQUIRE(n_q >= 0 && n_out >= 0 && ld_out >= n_out, "bad output shape %lld x %lld (ld %lld)", (long long)n_q,
                 (long long)n_out, (long long)ld_out);
-    QRY_REQUIRE(col_pos || n_out <= n_cols, "n_out %lld exceeds the block's %lld columns and there is no column map",
+    REQUIRE(col_pos || n_out <= n_cols, "n_out %lld exceeds the block's %lld columns and there is no column map",
                 (long long)n_out, (long long)n_cols);
     if (n_q == 0 || n_out == 0) return SIMRANK_QUERY_OK;
-    QRY_REQUIRE(row_pos && out, "row_pos or out is NULL");
+    REQUIRE(row_pos && out, "row_pos or out is NULL");
     const int64_t chunks = (n_out + kRowsChunk - 1) / kRowsChunk;
     const int64_t blocks = ((n_q + 7) / 8) * 8 * chunks;
-    QRY_REQUIRE(blocks < (int64_t(1) << 31), "%lld x %lld values are too many for one call: cut the query rows into bands",
+    REQUIRE(blocks < (int64_t(1) << 31), "%lld x %lld values are too many for one call: cut the query rows into bands",
                 (long long)n_q, (long long)n_out);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = as_stream(stream);
     QRY_DISPATCH(layout, query_rows_kernel, dim3((unsigned)blocks), dim3(kRowsThreads), st, S, stride, n_rows, n_cols, row_pos,
                  n_q, col_pos, n_out, chunks, out, ld_out);
-    QRY_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_QUERY_OK;
 }
 
@@ -234,13 +193,13 @@ int simrank_query_pairs(const void* S, int32_t layout, int64_t stride, int64_t n
                         const int32_t* b_pos, int64_t n_pairs, double* out, void* stream) {
     const int rc = check_block(S, layout, stride, n_rows, n_cols);
     if (rc) return rc;
-    QRY_REQUIRE(n_pairs >= 0 && n_pairs < (int64_t(1) << 38), "bad number of pairs %lld", (long long)n_pairs);
+    REQUIRE(n_pairs >= 0 && n_pairs < (int64_t(1) << 38), "bad number of pairs %lld", (long long)n_pairs);
     if (n_pairs == 0) return SIMRANK_QUERY_OK;
-    QRY_REQUIRE(a_pos && b_pos && out, "a_pos, b_pos or out is NULL");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    REQUIRE(a_pos && b_pos && out, "a_pos, b_pos or out is NULL");
+    hipStream_t st = as_stream(stream);
     const unsigned grid = (unsigned)((n_pairs + 255) / 256);
     QRY_DISPATCH(layout, query_pairs_kernel, dim3(grid), dim3(256), st, S, stride, n_rows, n_cols, a_pos, b_pos, n_pairs, out);
-    QRY_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_QUERY_OK;
 }
 
@@ -249,24 +208,24 @@ int simrank_query_topk(const void* S, int32_t layout, int64_t stride, int64_t n_
                        double* val_out, void* stream) {
     const int rc = check_block(S, layout, stride, n_rows, n_cols);
     if (rc) return rc;
-    QRY_REQUIRE(k >= 1 && k <= 1024, "k must be in [1, 1024] (got %d)", (int)k);
-    QRY_REQUIRE(n_q >= 0 && n_q < (int64_t(1) << 31), "bad number of query rows %lld", (long long)n_q);
+    REQUIRE(k >= 1 && k <= 1024, "k must be in [1, 1024] (got %d)", (int)k);
+    REQUIRE(n_q >= 0 && n_q < (int64_t(1) << 31), "bad number of query rows %lld", (long long)n_q);
     if (n_q == 0) return SIMRANK_QUERY_OK;
-    QRY_REQUIRE(row_pos && row_ids && idx_out && val_out, "row_pos, row_ids, idx_out or val_out is NULL");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    REQUIRE(row_pos && row_ids && idx_out && val_out, "row_pos, row_ids, idx_out or val_out is NULL");
+    hipStream_t st = as_stream(stream);
     const unsigned grid = (unsigned)std::min<int64_t>((n_q + 3) / 4, int64_t(1) << 16);
     QRY_DISPATCH(layout, query_topk_kernel, dim3(grid), dim3(256), st, S, stride, n_rows, n_cols, row_pos, row_ids, n_q, col_ids,
                  (int)k, idx_out, val_out);
-    QRY_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_QUERY_OK;
 }
 
 int simrank_query_merge_topk(int32_t n_pieces, const int32_t* const* ids, const double* const* vals, const int32_t* ks,
                              int64_t n_q, int32_t k, int32_t* idx_out, double* val_out) {
-    QRY_REQUIRE(n_pieces >= 0 && n_q >= 0 && k >= 1, "bad merge arguments");
-    QRY_REQUIRE(n_q == 0 || (idx_out && val_out), "idx_out or val_out is NULL");
+    REQUIRE(n_pieces >= 0 && n_q >= 0 && k >= 1, "bad merge arguments");
+    REQUIRE(n_q == 0 || (idx_out && val_out), "idx_out or val_out is NULL");
     for (int32_t p = 0; p < n_pieces; ++p)
-        QRY_REQUIRE(ks && ks[p] >= 0 && (n_q == 0 || ks[p] == 0 || (ids && vals && ids[p] && vals[p])), "bad piece %d", (int)p);
+        REQUIRE(ks && ks[p] >= 0 && (n_q == 0 || ks[p] == 0 || (ids && vals && ids[p] && vals[p])), "bad piece %d", (int)p);
     std::vector<std::pair<double, int32_t>> row;
     for (int64_t q = 0; q < n_q; ++q) {
         row.clear();

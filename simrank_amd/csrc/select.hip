@@ -8,14 +8,11 @@
 //             inside the wave (no atomics: one deterministic output)
 // The scan of the counts into int64 offsets and the move into the caller's order (whole row segments, then a sort
 // of each row by caller id on up to 16 host threads) are host code of this file.
-#include <hip/hip_runtime.h>
-
 #include <sched.h>
 
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -25,36 +22,15 @@
 
 #include "simrank_select.h"
 
+#define COMPANION_ERR_INVALID SIMRANK_SELECT_ERR_INVALID
+#define COMPANION_ERR_HIP SIMRANK_SELECT_ERR_HIP
+#include "companion.h"
+
 namespace {
 
-thread_local std::string g_error;
-
-void set_error(const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_error = buf;
-}
-
-#define SEL_REQUIRE(cond, ...)          \
-    do {                                \
-        if (!(cond)) {                  \
-            set_error(__VA_ARGS__);     \
-            return SIMRANK_SELECT_ERR_INVALID; \
-        }                               \
-    } while (0)
-
-#define SEL_HIP(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error("%s failed: %s", #call, hipGetErrorString(e_));                      \
-            (void)hipGetLastError();                                                       \
-            return SIMRANK_SELECT_ERR_HIP;                                                 \
-        }                                                                                  \
-    } while (0)
+COMPANION_SAME_LAYOUT(SIMRANK_SELECT_, PANEL_F32);
+COMPANION_SAME_LAYOUT(SIMRANK_SELECT_, ROWMAJOR_F32);
+COMPANION_SAME_LAYOUT(SIMRANK_SELECT_, PANEL_F16);
 
 typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
 
@@ -174,16 +150,16 @@ __global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ S,
 }
 
 int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, float t32) {
-    SEL_REQUIRE(layout == SIMRANK_SELECT_PANEL_F32 || layout == SIMRANK_SELECT_ROWMAJOR_F32 ||
+    REQUIRE(layout == SIMRANK_SELECT_PANEL_F32 || layout == SIMRANK_SELECT_ROWMAJOR_F32 ||
                     layout == SIMRANK_SELECT_PANEL_F16, "unknown layout %d", (int)layout);
-    SEL_REQUIRE(n_rows > 0 && n_cols >= 0 && n_cols < (int64_t(1) << 31) && n_rows < (int64_t(1) << 31),
+    REQUIRE(n_rows > 0 && n_cols >= 0 && n_cols < (int64_t(1) << 31) && n_rows < (int64_t(1) << 31),
                 "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    SEL_REQUIRE(n_cols == 0 || S, "S is NULL");
-    SEL_REQUIRE(layout == SIMRANK_SELECT_ROWMAJOR_F32 ? stride >= n_cols : stride >= n_rows,
+    REQUIRE(n_cols == 0 || S, "S is NULL");
+    REQUIRE(layout == SIMRANK_SELECT_ROWMAJOR_F32 ? stride >= n_cols : stride >= n_rows,
                 "stride %lld is too small for %lld x %lld", (long long)stride, (long long)n_rows, (long long)n_cols);
-    SEL_REQUIRE(layout == SIMRANK_SELECT_ROWMAJOR_F32 || (reinterpret_cast<uintptr_t>(S) & 15) == 0,
+    REQUIRE(layout == SIMRANK_SELECT_ROWMAJOR_F32 || (reinterpret_cast<uintptr_t>(S) & 15) == 0,
                 "a panel-blocked block must be 16-byte aligned");
-    SEL_REQUIRE(t32 > 0.f, "the threshold must be > 0");
+    REQUIRE(t32 > 0.f, "the threshold must be > 0");
     return SIMRANK_SELECT_OK;
 }
 
@@ -195,7 +171,7 @@ int launch(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_
     const int64_t waves = (n_rows + rows_per_wave - 1) / rows_per_wave;
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 256 * 8));
     const int vec = layout == SIMRANK_SELECT_ROWMAJOR_F32 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15) == 0;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    hipStream_t st = as_stream(stream);
 #define SEL_LAUNCH(LAYOUT)                                                                                            \
     hipLaunchKernelGGL((select_kernel<LAYOUT, EMIT>), dim3(grid), dim3(256), 0, st, S, stride, n_rows, n_cols, row_ids, \
                        col_ids, t32, counts, offsets, capacity, ids_out, vals_out, vec)
@@ -203,7 +179,7 @@ int launch(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_
     else if (layout == SIMRANK_SELECT_ROWMAJOR_F32) SEL_LAUNCH(SIMRANK_SELECT_ROWMAJOR_F32);
     else SEL_LAUNCH(SIMRANK_SELECT_PANEL_F16);
 #undef SEL_LAUNCH
-    SEL_HIP(hipGetLastError());
+    HIP_CHECK(hipGetLastError());
     return SIMRANK_SELECT_OK;
 }
 
@@ -231,8 +207,8 @@ int simrank_select_version(void) { return SIMRANK_SELECT_VERSION; }
 const char* simrank_select_last_error(void) { return g_error.c_str(); }
 
 int simrank_select_threshold_f32(double t, float* t32) {
-    SEL_REQUIRE(t32, "t32 is NULL");
-    SEL_REQUIRE(std::isfinite(t) && t > 0.0, "the threshold must be a finite number > 0 (got %g)", t);
+    REQUIRE(t32, "t32 is NULL");
+    REQUIRE(std::isfinite(t) && t > 0.0, "the threshold must be a finite number > 0 (got %g)", t);
     // (float)t is the nearest float: the smallest float >= t is it or the next one up (t > FLT_MAX: +inf)
     float f = (float)t;
     if ((double)f < t) f = std::nextafter(f, HUGE_VALF);
@@ -245,9 +221,9 @@ int simrank_select_count(const void* S, int32_t layout, int64_t stride, int64_t 
                          const int32_t* row_ids, const int32_t* col_ids, float t32, int32_t* counts, void* stream) {
     const int rc = check_block(S, layout, stride, n_rows, n_cols, t32);
     if (rc) return rc;
-    SEL_REQUIRE(counts, "counts is NULL");
+    REQUIRE(counts, "counts is NULL");
     if (n_cols == 0) {
-        SEL_HIP(hipMemsetAsync(counts, 0, size_t(n_rows) * sizeof(int32_t), reinterpret_cast<hipStream_t>(stream)));
+        HIP_CHECK(hipMemsetAsync(counts, 0, size_t(n_rows) * sizeof(int32_t), as_stream(stream)));
         return SIMRANK_SELECT_OK;
     }
     return launch<false>(S, layout, stride, n_rows, n_cols, row_ids, col_ids, t32, counts, nullptr, 0, nullptr, nullptr,
@@ -255,11 +231,11 @@ int simrank_select_count(const void* S, int32_t layout, int64_t stride, int64_t 
 }
 
 int simrank_select_offsets(const int32_t* counts, int64_t n_rows, int64_t* offsets, int64_t* total) {
-    SEL_REQUIRE(counts && offsets && n_rows >= 0, "bad offsets arguments");
+    REQUIRE(counts && offsets && n_rows >= 0, "bad offsets arguments");
     int64_t s = 0;
     offsets[0] = 0;
     for (int64_t r = 0; r < n_rows; ++r) {
-        SEL_REQUIRE(counts[r] >= 0, "count %d of row %lld is negative", (int)counts[r], (long long)r);
+        REQUIRE(counts[r] >= 0, "count %d of row %lld is negative", (int)counts[r], (long long)r);
         s += counts[r];
         offsets[r + 1] = s;
     }
@@ -272,7 +248,7 @@ int simrank_select_emit(const void* S, int32_t layout, int64_t stride, int64_t n
                         int32_t* ids_out, float* vals_out, void* stream) {
     const int rc = check_block(S, layout, stride, n_rows, n_cols, t32);
     if (rc) return rc;
-    SEL_REQUIRE(offsets && capacity >= 0 && (capacity == 0 || (ids_out && vals_out)), "bad emit arguments");
+    REQUIRE(offsets && capacity >= 0 && (capacity == 0 || (ids_out && vals_out)), "bad emit arguments");
     if (n_cols == 0 || capacity == 0) return SIMRANK_SELECT_OK;
     return launch<true>(S, layout, stride, n_rows, n_cols, row_ids, col_ids, t32, nullptr, offsets, capacity, ids_out,
                         vals_out, stream);
@@ -281,22 +257,22 @@ int simrank_select_emit(const void* S, int32_t layout, int64_t stride, int64_t n
 int simrank_select_merge(int32_t n_pieces, const int64_t* const* offsets, const int32_t* const* ids,
                          const float* const* vals, int64_t n_rows, const int32_t* row_order, int64_t* out_offsets,
                          int32_t* out_ids, float* out_vals, int32_t threads) {
-    SEL_REQUIRE(n_pieces > 0 && offsets && ids && vals && n_rows >= 0 && (row_order || !n_rows) && out_offsets,
+    REQUIRE(n_pieces > 0 && offsets && ids && vals && n_rows >= 0 && (row_order || !n_rows) && out_offsets,
                 "bad merge arguments");
     int64_t total = 0;
     for (int32_t p = 0; p < n_pieces; ++p) {
-        SEL_REQUIRE(offsets[p] && offsets[p][0] == 0, "piece %d: offsets must start at 0", (int)p);
+        REQUIRE(offsets[p] && offsets[p][0] == 0, "piece %d: offsets must start at 0", (int)p);
         for (int64_t r = 0; r < n_rows; ++r)
-            SEL_REQUIRE(offsets[p][r + 1] >= offsets[p][r], "piece %d: offsets decrease at row %lld", (int)p, (long long)r);
-        SEL_REQUIRE(offsets[p][n_rows] == 0 || (ids[p] && vals[p]), "piece %d: ids or values are NULL", (int)p);
+            REQUIRE(offsets[p][r + 1] >= offsets[p][r], "piece %d: offsets decrease at row %lld", (int)p, (long long)r);
+        REQUIRE(offsets[p][n_rows] == 0 || (ids[p] && vals[p]), "piece %d: ids or values are NULL", (int)p);
         total += offsets[p][n_rows];
     }
-    SEL_REQUIRE(total == 0 || (out_ids && out_vals), "out_ids or out_vals is NULL");
+    REQUIRE(total == 0 || (out_ids && out_vals), "out_ids or out_vals is NULL");
     // row lengths in the caller's order, then their scan
     std::vector<char> seen((size_t)n_rows, 0);
     for (int64_t r = 0; r < n_rows; ++r) {
         const int32_t a = row_order[r];
-        SEL_REQUIRE(a >= 0 && a < n_rows && !seen[(size_t)a], "row_order is not a permutation of 0 .. %lld",
+        REQUIRE(a >= 0 && a < n_rows && !seen[(size_t)a], "row_order is not a permutation of 0 .. %lld",
                     (long long)n_rows - 1);
         seen[(size_t)a] = 1;
         int64_t len = 0;
@@ -339,7 +315,7 @@ int simrank_select_merge(int32_t n_pieces, const int64_t* const* offsets, const 
     for (int64_t t = 1; t < nt; ++t) pool.emplace_back(crew);
     crew();
     for (auto& t : pool) t.join();
-    SEL_REQUIRE(!bad.load(), "a row holds the same id twice");
+    REQUIRE(!bad.load(), "a row holds the same id twice");
     return SIMRANK_SELECT_OK;
 }
 

@@ -57,6 +57,18 @@ class SideSpec:
     storage: str = "f32"         # "fp16": S and the transposed product held in fp16 (config 5)
 
 
+def prior_matrix(spec: SideSpec, dtype):
+    """The side's prior as a solver takes it: ``dtype``, C-contiguous, n x n, or None (SimRank.py:453 blends a float64
+    array; float32 is the rounding to the plans' storage precision).  Another shape: NumPy's broadcast error."""
+    if spec.apriori is None:
+        return None
+    a = np.asarray(spec.apriori)
+    n = spec.csr.n_rows
+    if a.shape != (n, n):
+        raise ValueError(f"operands could not be broadcast together with shapes ({n},{n}) {a.shape} ")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
 class LocalWorld:
     """P ranks inside this process on one device (P = 1 is the ordinary single-GPU case; P > 1: virtual ranks — the
     sharded C loop on an in-process group whose exchanges are device copies: tests and single-GPU emulation)."""

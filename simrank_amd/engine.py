@@ -149,9 +149,8 @@ def _query_reader(ops, getters):
     n = blocks[0]["rows"]
     order = np.empty(n, dtype=np.int32)
     if n:
-        check(ops.lib.simrank_memcpy_d2h(order.ctypes.data, C.c_void_p(blocks[0]["row_ids"]), 4 * n, ops.stream),
-              "simrank_memcpy_d2h")
-        check(ops.lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+        ops.d2h(order, blocks[0]["row_ids"])
+        ops.synchronize()
     return _query.Reader(ops, blocks, order)
 
 
@@ -170,49 +169,38 @@ class Selection:
         self.n = n = blocks[0]["rows"]
         self.count_ms = self.emit_ms = 0.0
         assert all(b["rows"] == n for b in blocks)
-        lib = ops.lib
         self.offsets = []
         cnt_dev = ops._malloc(4 * n)
         counts = np.empty(n, dtype=np.int32)
         try:
             for b in blocks:
-                self._timed("count_ms", lambda: _select.check(self.sel.simrank_select_count(
+                self._pass("count_ms", lambda: _select.check(self.sel.simrank_select_count(
                     b["ptr"], b["layout"], b["stride"], n, b["cols"], b["row_ids"], b["col_ids"], self.t32, cnt_dev,
                     ops.stream), "simrank_select_count"))
-                check(lib.simrank_memcpy_d2h(counts.ctypes.data, C.c_void_p(cnt_dev), 4 * n, ops.stream), "simrank_memcpy_d2h")
-                check(lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+                ops.d2h(counts, cnt_dev)
+                ops.synchronize()
                 off = np.empty(n + 1, dtype=np.int64)
                 _select.check(self.sel.simrank_select_offsets(counts.ctypes.data, n, off.ctypes.data, None),
                               "simrank_select_offsets")
                 self.offsets.append(off)
             # the rows' caller ids (the same for every block: one solver order)
             self.row_order = np.empty(n, dtype=np.int32)
-            check(lib.simrank_memcpy_d2h(self.row_order.ctypes.data, C.c_void_p(blocks[0]["row_ids"]), 4 * n, ops.stream),
-                  "simrank_memcpy_d2h")
-            check(lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+            ops.d2h(self.row_order, blocks[0]["row_ids"])
+            ops.synchronize()
         finally:
             ops._free(cnt_dev)
         self.total = sum(int(o[-1]) for o in self.offsets)
 
-    def _timed(self, key, launch):
+    def _pass(self, key, launch):
         if not self.timing:
             launch()
-            return
-        a, b = self.ops.event(), self.ops.event()
-        try:
-            self.ops.record(a)
-            launch()
-            self.ops.record(b)
-            self.ops.event_synchronize(b)
-            setattr(self, key, getattr(self, key) + self.ops.elapsed_ms(a, b))
-        finally:
-            self.ops.event_destroy(a)
-            self.ops.event_destroy(b)
+        else:
+            setattr(self, key, getattr(self, key) + self.ops.timed(launch))
 
     def emit(self):
         """[(offsets int64 [n + 1], caller ids int32, values float32)] per block, rows in the solver's order."""
         from . import _select
-        ops, lib, n = self.ops, self.ops.lib, self.n
+        ops, n = self.ops, self.n
         pieces = []
         for b, off in zip(self.blocks, self.offsets):
             tot = int(off[-1])
@@ -222,14 +210,13 @@ class Selection:
                 bufs = [ops._malloc(8 * (n + 1)), ops._malloc(4 * tot), ops._malloc(4 * tot)]
                 try:
                     off_dev, ids_dev, val_dev = bufs
-                    check(lib.simrank_memcpy_h2d(C.c_void_p(off_dev), off.ctypes.data, 8 * (n + 1), ops.stream),
-                          "simrank_memcpy_h2d")
-                    self._timed("emit_ms", lambda: _select.check(self.sel.simrank_select_emit(
+                    ops.h2d(off_dev, off)
+                    self._pass("emit_ms", lambda: _select.check(self.sel.simrank_select_emit(
                         b["ptr"], b["layout"], b["stride"], n, b["cols"], b["row_ids"], b["col_ids"], self.t32, off_dev,
                         tot, ids_dev, val_dev, ops.stream), "simrank_select_emit"))
-                    check(lib.simrank_memcpy_d2h(ids.ctypes.data, C.c_void_p(ids_dev), 4 * tot, ops.stream), "simrank_memcpy_d2h")
-                    check(lib.simrank_memcpy_d2h(vals.ctypes.data, C.c_void_p(val_dev), 4 * tot, ops.stream), "simrank_memcpy_d2h")
-                    check(lib.simrank_stream_synchronize(ops.stream), "simrank_stream_synchronize")
+                    ops.d2h(ids, ids_dev)
+                    ops.d2h(vals, val_dev)
+                    ops.synchronize()
                 finally:
                     for ptr in bufs:
                         ops._free(ptr)
@@ -943,6 +930,22 @@ class HipOps:
             check(self.lib.simrank_memcpy_d2d(C.c_void_p(dst_ptr), C.c_void_p(src_ptr), nbytes,
                                               self.stream), "d2d")
 
+    # ---- plain transfers on the engine's stream (what the callers of the companion libraries move) ----
+    def h2d(self, ptr: int, host: np.ndarray):
+        """Device memory at ``ptr`` = the C-contiguous host array."""
+        check(self.lib.simrank_memcpy_h2d(C.c_void_p(ptr), host.ctypes.data, host.nbytes, self.stream), "simrank_memcpy_h2d")
+
+    def d2h(self, host: np.ndarray, ptr: int, nbytes: int | None = None):
+        """The C-contiguous host array (its first ``nbytes``) = device memory at ``ptr``."""
+        check(self.lib.simrank_memcpy_d2h(host.ctypes.data, C.c_void_p(ptr), host.nbytes if nbytes is None else nbytes,
+                                          self.stream), "simrank_memcpy_d2h")
+
+    def put(self, host: np.ndarray) -> int:
+        """A device block (``_free`` it) holding a copy of the host array."""
+        ptr = self._malloc(host.nbytes)
+        self.h2d(ptr, host)
+        return ptr
+
     def upload(self, m: Matrix, host: np.ndarray):
         host = np.asarray(host)
         assert host.shape == (m.rows, m.cols), (host.shape, m.rows, m.cols)
@@ -951,8 +954,7 @@ class HipOps:
             for pnl in range(m.panels):
                 w = min(64, m.cols - 64 * pnl)
                 buf[pnl, :m.rows, :w] = host[:, 64 * pnl:64 * pnl + w].astype(np.float32) * np.float32(m.scale)
-            check(self.lib.simrank_memcpy_h2d(m.ptr, buf.ctypes.data, buf.nbytes, self.stream),
-                  "simrank_memcpy_h2d")
+            self.h2d(m.ptr, buf)
             return
         if m.blocked:                       # through a row-major copy on the device
             tmp = self.matrix(m.rows, m.cols, m.dtype)
@@ -963,8 +965,7 @@ class HipOps:
             return
         buf = np.zeros((m.rows, m.ld), dtype=m.dtype)
         buf[:, :m.cols] = host
-        check(self.lib.simrank_memcpy_h2d(m.ptr, buf.ctypes.data, buf.nbytes, self.stream),
-              "simrank_memcpy_h2d")
+        self.h2d(m.ptr, buf)
 
     def widen(self, src: Matrix) -> Matrix:
         """float32 panel-blocked copy of a float16 matrix (what the hand-back entries read)."""
@@ -988,8 +989,7 @@ class HipOps:
             tmp.free()
             return out
         buf = np.empty((m.rows, m.ld), dtype=m.dtype)
-        check(self.lib.simrank_memcpy_d2h(buf.ctypes.data, m.ptr, buf.nbytes, self.stream),
-              "simrank_memcpy_d2h")
+        self.d2h(buf, m.ptr)
         return buf[:, :m.cols] if m.ld == m.cols else np.ascontiguousarray(buf[:, :m.cols])
 
     def download_rows(self, m: Matrix, rows) -> np.ndarray:
@@ -1010,8 +1010,7 @@ class HipOps:
         out = np.empty((len(rows), m.cols), dtype=m.dtype)
         isz = m.dtype.itemsize
         for i, r in enumerate(rows):
-            check(self.lib.simrank_memcpy_d2h(out[i].ctypes.data, C.c_void_p(m.ptr + int(r) * m.ld * isz),
-                                              m.cols * isz, self.stream), "simrank_memcpy_d2h")
+            self.d2h(out[i], m.ptr + int(r) * m.ld * isz)
         return out
 
     def topk_rows(self, m: Matrix, k: int, col0: int = 0, exclude_diag: bool = True,
@@ -1349,6 +1348,19 @@ class HipOps:
         check(self.lib.simrank_event_elapsed_ms(C.c_void_p(start), C.c_void_p(stop),
                                                 C.byref(ms)), "event_elapsed")
         return float(ms.value)
+
+    def timed(self, launch) -> float:
+        """Milliseconds of what ``launch()`` queues on the engine's stream, between two events (waits for the second)."""
+        a, b = self.event(), self.event()
+        try:
+            self.record(a)
+            launch()
+            self.record(b)
+            self.event_synchronize(b)
+            return self.elapsed_ms(a, b)
+        finally:
+            self.event_destroy(a)
+            self.event_destroy(b)
 
     def close(self):
         """Release the stream and the counter (matrices and graphs free themselves)."""

@@ -2,50 +2,33 @@
 plain C, argument checks need no device, and ``fit(storage_precision="f64")`` refuses what it does not run before any
 device work.  The main library stays at ABI 8 with 117 entry points, the select library at version 1."""
 import ctypes
-import os
 import re
-import subprocess
 
 import numpy as np
 import pandas as pd
 import pytest
 
 from simrank_amd import _f64, _lib, _select
-
-
-def _declared():
-    text = open(_f64.HEADER_PATH).read()
-    return sorted(set(re.findall(r"^SIMRANK_F64_API [\w \*]+?\b(simrank_f64_\w+)\(", text, flags=re.M)))
+from tests import companion_abi as A
 
 
 def test_header_binding_and_exports_agree():
-    assert _declared() == sorted(_f64.PROTOTYPES)
-    out = subprocess.run(["nm", "-D", "--defined-only", _f64.LIB_PATH], capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r" T (simrank_\w+)", out)))
-    assert exported == _declared()
-    assert _f64.load().simrank_f64_version() == _f64.VERSION == 1
-    assert re.search(r"#define SIMRANK_F64_VERSION 1\b", open(_f64.HEADER_PATH).read())
+    assert A.loaded_version(_f64) == _f64.VERSION == 1
 
 
 def test_companion_links_nothing_of_the_main_library():
-    out = subprocess.run(["readelf", "-d", _f64.LIB_PATH], capture_output=True, text=True).stdout
-    assert "libsimrank_hip" not in out
-    assert '#include "simrank_hip.h"' not in open(_f64.HEADER_PATH).read()
+    A.assert_links_nothing_of_the_main_library(_f64)
 
 
 def test_main_library_and_select_library_are_unchanged():
-    lib = _lib.load()
-    assert lib.simrank_abi_version() == _lib.ABI_VERSION == 8
-    text = open(_lib.HEADER_PATH).read()
-    assert len(set(re.findall(r"^SIMRANK_API [\w \*]+?\b(simrank_\w+)\(", text, flags=re.M))) == 117
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    assert not [s for s in re.findall(r" T (simrank_\w+)", out) if s.startswith("simrank_f64")]
+    version, names, exports = A.main_library(_f64)
+    assert version == _lib.ABI_VERSION == 8
+    assert len(names) == 117 and len(exports) == 117
     assert _select.load().simrank_select_version() == _select.VERSION == 1
 
 
 def test_header_is_c99_and_a_c_program_links(tmp_path):
-    src = tmp_path / "use_f64.c"
-    src.write_text(r'''
+    assert "f64 1 ok" in A.run_c99(_f64, tmp_path, r'''
 #include <stdio.h>
 #include <string.h>
 #include "simrank_f64.h"
@@ -68,14 +51,6 @@ int main(void) {
     return 0;
 }
 ''')
-    exe = tmp_path / "use_f64"
-    libdir = os.path.dirname(_f64.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                         f"-I{os.path.dirname(_f64.HEADER_PATH)}", str(src), "-o", str(exe), f"-L{libdir}",
-                         "-lsimrank_f64", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert run.returncode == 0 and "f64 1 ok" in run.stdout, (run.returncode, run.stdout, run.stderr)
 
 
 def _side(n_rows=3, n_cols=3, rowptr=(0, 1, 2, 3), col=(1, 2, 0), **kw):

@@ -1,9 +1,7 @@
 """libsimrank_foldin.so (include/simrank_foldin.h) and ``fold_in`` on a machine without a GPU: header, binding and exports
 agree, the header is plain C99 and stands alone, the NumPy statement of the formula (tests/foldin_ref.py) is the
 reference's own next update, and every argument check of ``fold_in`` runs before any device work."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pandas as pd
@@ -11,28 +9,17 @@ import pytest
 
 import simrank_amd.SimRank as SRA
 from simrank_amd import _foldin
+from tests import companion_abi as A
 from tests import foldin_ref as R
 from tests.conftest import Golden
 
 
-def _declared():
-    text = open(_foldin.HEADER_PATH).read()
-    return sorted(set(re.findall(r"^SIMRANK_FOLDIN_API [\w \*]+?\b(simrank_foldin_\w+)\(", text, flags=re.M)))
-
-
 def test_header_binding_and_exports_agree():
-    assert _declared() == sorted(_foldin.PROTOTYPES)
-    out = subprocess.run(["nm", "-D", "--defined-only", _foldin.LIB_PATH], capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r" T (\w+)", out)))
-    assert exported == _declared()
-    assert _foldin.load().simrank_foldin_version() == _foldin.VERSION == 1
-    text = open(_foldin.HEADER_PATH).read()
-    assert re.search(r"#define SIMRANK_FOLDIN_VERSION 1\b", text)
+    assert A.loaded_version(_foldin) == _foldin.VERSION == 1
+    text = A.header(_foldin)
     assert re.search(r"#define SIMRANK_FOLDIN_TILE %d\b" % _foldin.TILE, text)
     assert re.search(r"#define SIMRANK_FOLDIN_LONG_ROW %d\b" % _foldin.LONG_ROW, text)
-    # the header stands alone: nothing of the project's other headers
-    assert not re.findall(r'#include\s+"', text)
-    assert set(re.findall(r"#include\s+<(\S+)>", text)) == {"stddef.h", "stdint.h"}
+    A.assert_header_stands_alone(_foldin)
     # the layouts are simrank_query.h's
     from simrank_amd import _query
     for name, value in (("PANEL_F32", _query.PANEL_F32), ("ROWMAJOR_F32", _query.ROWMAJOR_F32),
@@ -41,18 +28,15 @@ def test_header_binding_and_exports_agree():
 
 
 def test_prototypes_match_the_header_argument_counts():
-    text = open(_foldin.HEADER_PATH).read()
-    for name, argtypes in _foldin.PROTOTYPES.items():
-        m = re.search(r"^SIMRANK_FOLDIN_API [\w \*]+?\b%s\(([^;]*?)\);" % name, text, flags=re.S | re.M)
-        assert m, name
-        args = m.group(1).strip()
-        n = 0 if args == "void" else len(args.split(","))
-        assert n == len(argtypes), (name, args)
+    A.assert_prototypes_match_the_header_argument_counts(_foldin)
+
+
+def test_companion_links_nothing_of_the_main_library():
+    A.assert_links_nothing_of_the_main_library(_foldin)
 
 
 def test_header_is_c99_and_a_c_program_links(tmp_path):
-    src = tmp_path / "use_foldin.c"
-    src.write_text(r'''
+    assert "foldin 1 ok" in A.run_c99(_foldin, tmp_path, r'''
 #include <stdio.h>
 #include <string.h>
 #include "simrank_foldin.h"
@@ -90,14 +74,6 @@ int main(void) {
     return 0;
 }
 ''')
-    exe = tmp_path / "use_foldin"
-    libdir = os.path.dirname(_foldin.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                         f"-I{os.path.dirname(_foldin.HEADER_PATH)}", str(src), "-o", str(exe), f"-L{libdir}",
-                         "-lsimrank_foldin", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert run.returncode == 0 and "foldin 1 ok" in run.stdout, (run.returncode, run.stdout, run.stderr)
 
 
 # ---- the NumPy statement of the formula is the reference's own next update ----------------------------------------

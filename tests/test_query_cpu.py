@@ -2,61 +2,54 @@
 exports agree, the header is plain C99 and stands alone, argument checks need no device, the host merge of per-block
 top-k candidates orders as a NumPy sort does, and ``fit(keep=True)`` refuses what it does not serve before any device
 work.  The main library's ABI stays at version 8 with 117 entry points."""
-import os
 import re
-import subprocess
 
 import numpy as np
 import pandas as pd
 import pytest
 
 import simrank_amd.SimRank as SRA
-from simrank_amd import _lib, _query
+from simrank_amd import _query
+from tests import companion_abi as A
 
 CLASSES = ["SimRank", "SimRankPP", "AprioriSimRank", "BipartiteSimRank", "BipartiteSimRankPP", "BipartitleAprioriSimRank"]
 
 
-def _declared():
-    text = open(_query.HEADER_PATH).read()
-    return sorted(set(re.findall(r"^SIMRANK_QUERY_API [\w \*]+?\b(simrank_query_\w+)\(", text, flags=re.M)))
-
-
 def test_header_binding_and_exports_agree():
-    assert _declared() == sorted(_query.PROTOTYPES)
-    out = subprocess.run(["nm", "-D", "--defined-only", _query.LIB_PATH], capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r" T (\w+)", out)))
-    assert exported == _declared()
-    assert _query.load().simrank_query_version() == _query.VERSION == 1
-    text = open(_query.HEADER_PATH).read()
-    assert re.search(r"#define SIMRANK_QUERY_VERSION 1\b", text)
-    # the header stands alone: nothing of the project's other headers
-    assert not re.findall(r'#include\s+"', text)
-    assert set(re.findall(r"#include\s+<(\S+)>", text)) == {"stddef.h", "stdint.h"}
+    assert A.loaded_version(_query) == _query.VERSION == 1
+    A.assert_header_stands_alone(_query)
 
 
 def test_prototypes_match_the_header_argument_counts():
-    text = open(_query.HEADER_PATH).read()
-    for name, argtypes in _query.PROTOTYPES.items():
-        m = re.search(r"^SIMRANK_QUERY_API [\w \*]+?\b%s\(([^;]*?)\);" % name, text, flags=re.S | re.M)
-        assert m, name
-        args = m.group(1).strip()
-        n = 0 if args == "void" else len(args.split(","))
-        assert n == len(argtypes), (name, args)
+    A.assert_prototypes_match_the_header_argument_counts(_query)
+
+
+def test_companion_links_nothing_of_the_main_library():
+    A.assert_links_nothing_of_the_main_library(_query)
+
+
+def test_layout_codes_agree_across_headers_and_bindings():
+    """One set of layout codes: ``engine._iterate_block`` hands a plan's "iterate_layout" to the select, query and
+    fold-in libraries alike, and ``_foldin.Folder`` passes a query code to fold-in calls (csrc/companion.h asserts the
+    same of the three headers when the libraries are compiled)."""
+    from simrank_amd import _companion, _foldin, _select
+    want = {"PANEL_F32": 0, "ROWMAJOR_F32": 1, "PANEL_F16": 2, "ROWMAJOR_F64": 3}
+    assert A.layout_codes(_query) == want and A.layout_codes(_foldin) == want
+    three = {k: v for k, v in want.items() if k != "ROWMAJOR_F64"}            # (select reads no float64 iterate)
+    assert A.layout_codes(_select) == three
+    for mod, names in ((_companion, want), (_query, want), (_select, three), (_foldin, ["ROWMAJOR_F64"])):
+        for name in names:
+            assert getattr(mod, name) == want[name], (mod.__name__, name)
 
 
 def test_main_library_abi_is_unchanged():
-    lib = _lib.load()
-    assert lib.simrank_abi_version() == 8
-    text = open(_lib.HEADER_PATH).read()
-    assert len(set(re.findall(r"^SIMRANK_API [\w \*]+?\b(simrank_\w+)\(", text, flags=re.M))) == 117
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    exported = set(re.findall(r" T (simrank_\w+)", out))
-    assert len(exported) == 117 and not [s for s in exported if s.startswith("simrank_query")]
+    version, names, exports = A.main_library(_query)
+    assert version == 8
+    assert len(names) == 117 and len(exports) == 117
 
 
 def test_header_is_c99_and_a_c_program_links(tmp_path):
-    src = tmp_path / "use_query.c"
-    src.write_text(r'''
+    assert "query 1 ok" in A.run_c99(_query, tmp_path, r'''
 #include <stdio.h>
 #include <string.h>
 #include "simrank_query.h"
@@ -88,14 +81,6 @@ int main(void) {
     return 0;
 }
 ''')
-    exe = tmp_path / "use_query"
-    libdir = os.path.dirname(_query.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                         f"-I{os.path.dirname(_query.HEADER_PATH)}", str(src), "-o", str(exe), f"-L{libdir}",
-                         "-lsimrank_query", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert run.returncode == 0 and "query 1 ok" in run.stdout, (run.returncode, run.stdout, run.stderr)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])

@@ -3,44 +3,31 @@ header is plain C, the threshold conversion is exact, argument checks need no de
 as the dense frame's masked ``np.nonzero``, and ``fit(min_similarity=...)`` refuses bad thresholds before any device
 work.  The main library's ABI stays at version 8 with 117 entry points."""
 import ctypes
-import os
-import re
-import subprocess
 
 import numpy as np
 import pandas as pd
 import pytest
 
-from simrank_amd import _lib, _select
-
-
-def _declared():
-    text = open(_select.HEADER_PATH).read()
-    return sorted(set(re.findall(r"^SIMRANK_SELECT_API [\w \*]+?\b(simrank_select_\w+)\(", text, flags=re.M)))
+from simrank_amd import _select
+from tests import companion_abi as A
 
 
 def test_header_binding_and_exports_agree():
-    assert _declared() == sorted(_select.PROTOTYPES)
-    out = subprocess.run(["nm", "-D", "--defined-only", _select.LIB_PATH], capture_output=True, text=True).stdout
-    exported = sorted(set(re.findall(r" T (simrank_\w+)", out)))
-    assert exported == _declared()
-    assert _select.load().simrank_select_version() == _select.VERSION == 1
-    text = open(_select.HEADER_PATH).read()
-    assert re.search(r"#define SIMRANK_SELECT_VERSION 1\b", text)
+    assert A.loaded_version(_select) == _select.VERSION == 1
+
+
+def test_companion_links_nothing_of_the_main_library():
+    A.assert_links_nothing_of_the_main_library(_select)
 
 
 def test_main_library_abi_is_unchanged():
-    lib = _lib.load()
-    assert lib.simrank_abi_version() == 8
-    text = open(_lib.HEADER_PATH).read()
-    assert len(set(re.findall(r"^SIMRANK_API [\w \*]+?\b(simrank_\w+)\(", text, flags=re.M))) == 117
-    out = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    assert not [s for s in re.findall(r" T (simrank_\w+)", out) if s.startswith("simrank_select")]
+    version, names, exports = A.main_library(_select)
+    assert version == 8
+    assert len(names) == 117 and len(exports) == 117
 
 
 def test_header_is_c99_and_a_c_program_links(tmp_path):
-    src = tmp_path / "use_select.c"
-    src.write_text(r'''
+    assert "select 1 ok" in A.run_c99(_select, tmp_path, r'''
 #include <stdio.h>
 #include <string.h>
 #include "simrank_select.h"
@@ -60,14 +47,6 @@ int main(void) {
     return 0;
 }
 ''')
-    exe = tmp_path / "use_select"
-    libdir = os.path.dirname(_select.LIB_PATH)
-    cc = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic",
-                         f"-I{os.path.dirname(_select.HEADER_PATH)}", str(src), "-o", str(exe), f"-L{libdir}",
-                         "-lsimrank_select", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert cc.returncode == 0, cc.stderr
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert run.returncode == 0 and "select 1 ok" in run.stdout, (run.returncode, run.stdout, run.stderr)
 
 
 def _smallest_f32_at_least(t):
