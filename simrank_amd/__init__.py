@@ -9,6 +9,6 @@ The iteration runs as hand-written HIP kernels for gfx950 behind the C ABI decla
 from . import SimRank  # noqa: F401
 from .estimators import (  # noqa: F401
     AprioriSimRank, BipartiteAprioriSimRank, BipartiteSimRank, BipartiteSimRankPP,
-    BipartitleAprioriSimRank, BipartitleSimRank, BipartitleSimRankPP, SimRankPP)
+    BipartitleAprioriSimRank, BipartitleSimRank, BipartitleSimRankPP, SimRankPP, load_model)
 
 __version__ = "0.1.0"

@@ -33,7 +33,8 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
     keep              False (default) | True: hand nothing back, keep the model on the device and return the estimator
                       itself, which then answers node queries without the N x N transfer (``_KeptModel``: ``rows``,
                       ``similarity``, ``most_similar``, ``fold_in`` (nodes that were NOT in the graph), ``frame``,
-                      ``top_k``, ``pairs``, ``release``; a context manager).
+                      ``top_k``, ``pairs``, ``release``; a context manager; ``compact`` cuts it down to one matrix per
+                      side, ``save`` / ``load_model`` write it to a file and read it back).
                       One GPU or ``LocalWorld(P)``, every storage precision; not with ``top_k`` / ``min_similarity``
                       (the kept model answers them)
     strict_reference  bipartite classes only; True keeps quirks Q1 (set-order labels on
@@ -431,6 +432,65 @@ class _KeptModel:
         _check_pairs_args(min_similarity, max_pairs)
         return self._all_sides(lambda solver, j, lab: _pairs_frame(solver, j, min_similarity, max_pairs, lab))
 
+    def compact(self, precision=None):
+        """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense
+        frame's order (libsimrank_model.so), then the plan's matrices are released (the evidence counts stay, so the lazy
+        ``Evidence`` attributes keep working).  Every query answers as before, bit for bit.  ``precision``: None keeps the
+        model's storage (f32, fp16-held or float64); "fp16" also narrows an f32 model to the fp16-held form (value x 2^14
+        in binary16, round to nearest even: relative error <= 2^-11 down to 2^-28, absolute <= 2^-39 below), a ValueError
+        that names the count, with the model left as it was, when a value does not fit, and a ValueError before any device
+        work on a float64 model.  Peak device memory during the call is the plan plus the copy; afterwards N^2 x (4 | 2 |
+        8) bytes per side plus, once ``fold_in`` ran, the side's CSR.  Idempotent; returns the estimator."""
+        from . import _model
+        _model.check_precision(precision)
+        if self._model is None:
+            self._kept(1)                                   # (raises: no kept model, or released)
+        solver, sides = self._model
+        if isinstance(solver, _model.DetachedSolver) and (precision is None or solver.storage == "fp16"):
+            return self
+        detached = _model.detach(solver, precision)         # (raises with the kept model intact)
+        self._model = (detached, sides)
+        solver.release()
+        return self
+
+    @property
+    def device_bytes(self):
+        """Bytes of device memory in the model's own matrices: the packed blocks of a compact model; of a model that still
+        holds its plan, the iterates the queries read (the plan holds more: see ``compact``)."""
+        from . import _model
+        if self._model is None:
+            self._kept(1)
+        solver, sides = self._model
+        if isinstance(solver, _model.DetachedSolver):
+            return solver.device_bytes
+        return sum(_model.block_bytes(b) for j, _ in sides for b in solver._reader(j).blocks)
+
+    def save(self, path):
+        """Write the model to one file ``load_model`` reads back (a JSON header, then raw little-endian arrays: the packed
+        iterates, the CSR and the row scales; no pickle).  A model that still holds its plan is packed into a temporary
+        block first and stays as it is.  Labels must be Python ``int`` (any size) or ``str``, or the integers of one NumPy
+        integer type; anything else is a ValueError that names the type."""
+        from . import _model
+        if self._model is None:
+            self._kept(1)
+        solver, sides = self._model
+        labels = [lab for _, lab in sides]
+        for lab in labels:
+            _model.encode_labels(lab)                       # (ValueError before any device work)
+        specs = solver.specs
+        meta = {"class": type(self).__name__, "weighted": bool(getattr(self, "_weighted", False)),
+                "strict": bool(len(specs) == 2 and specs[1].evidence_from is not None
+                               and specs[1].evidence_from is specs[0].csr),
+                "converged_at": getattr(self, "converged_at", None), "engine_mode": getattr(self, "engine_mode", None)}
+        if isinstance(solver, _model.DetachedSolver):
+            _model.save(path, solver, meta, labels)
+            return
+        temp = _model.detach(solver)
+        try:
+            _model.save(path, temp, meta, labels)
+        finally:
+            temp.release()
+
     def release(self):
         """Free the kept model's device memory (the lazy ``Evidence`` attributes keep working); queries raise afterwards."""
         if self._model is not None:
@@ -776,6 +836,36 @@ def _host_evidence(csr):
     pat = sp.csr_matrix((live.astype(np.int64), csr.col, csr.rowptr),
                         shape=(csr.n_rows, csr.n_cols))
     return 1 - 0.5 ** np.asarray((pat @ pat.T).todense(), dtype=np.float64)
+
+
+def _not_fitted(name):
+    def read():
+        raise AttributeError(f"{name}: this model was loaded from a file, not fitted; the fit-time attributes of the "
+                             f"reference (Graph, Weight, Evidence, ...) exist after fit() only")
+    return read
+
+
+def load_model(path, device=None):
+    """The estimator ``model.save(path)`` wrote, holding a compact model on ``device`` (default: LOCAL_RANK or 0): an
+    instance of the saved class that answers every query of a kept model (``rows``, ``similarity``, ``most_similar``,
+    ``fold_in``, ``frame``, ``top_k``, ``pairs``, ``release``, ``with``).  No plan is built.  The reference's fit-time
+    attributes (``Graph``, ``Weight``, ``Evidence`` ...) raise AttributeError.  A file that is truncated, is no saved model,
+    has a newer format or whose arrays disagree with its header is a ValueError before any device allocation."""
+    from . import _model
+    meta, solver, labels = _model.load_file(path, device)
+    est = globals()[meta["class"]]()
+    for klass in type(est).__mro__:
+        for name, attr in vars(klass).items():
+            if isinstance(attr, _Lazy):
+                setattr(est, name, _not_fitted(name))
+    if len(labels) == 1:
+        est.Nodes = set(labels[0])
+    else:
+        est.NodesGroup1, est.NodesGroup2 = set(labels[0]), set(labels[1])
+    est._weighted = bool(meta["weighted"])
+    est.converged_at = meta.get("converged_at")
+    est.engine_mode = meta.get("engine_mode") or solver.mode
+    return est._keep(solver, list(enumerate(labels)))
 
 
 # spellings used by the reference README (README.md:16) and BASELINE.json
