@@ -112,6 +112,12 @@ class SolverQueries:
             self._folders[j] = _foldin.Folder(self._reader(src), spec.csr, spec.rowscale, spec.coef, spec.lbd, evidence)
         return self._folders[j].run(lists, w, prior, top_k, timing)
 
+    def score_sets(self, j, ptr, ids, w, k=None, excl=None, timing=None):
+        """Basket scores on side j's iterate (``_sets.run``): ``ptr`` / ``ids`` / ``w`` the baskets as offsets, node ids
+        of side j and weights; the dense rows, or with ``k`` the k best per basket outside ``excl``."""
+        from . import _sets
+        return _sets.run(self._reader(j), ptr, ids, w, k, excl, timing)
+
     def _close_readers(self):
         folders, self._folders = self._folders or {}, None
         for f in folders.values():

@@ -411,6 +411,71 @@ class _KeptModel:
             "neighbor": out_index.take(idx.ravel()[keep]),
             "similarity": val.ravel()[keep]})
 
+    @staticmethod
+    def _best_frame(first, who, out_index, idx, val, keep_rows=None):
+        """Long frame (``first``, rank, neighbor, score) of a device selection: ``who`` the label of every row of ``idx``."""
+        n, kk = idx.shape
+        keep = idx.ravel() >= 0
+        if keep_rows is not None:
+            keep &= np.repeat(np.asarray(keep_rows, dtype=bool), kk)
+        return pd.DataFrame({
+            first: who.take(np.repeat(np.arange(n), kk)[keep]),
+            "rank": np.tile(np.arange(1, kk + 1), n)[keep],
+            "neighbor": out_index.take(idx.ravel()[keep]),
+            "score": val.ravel()[keep]})
+
+    def score_sets(self, sets, weights=None, names=None, group=None, top_k=None, exclude="members"):
+        """Basket queries: for each basket (a sequence of labels of FITTED nodes of ``group``, repeats counting as often
+        as they occur) the row
+
+            score(b) = sum_{i in basket} w_i * S[i, b]
+
+        of that group's matrix, summed on the device in float64 in the order given, every product and every sum rounded
+        separately: bit for bit what ``(w[:, None] * model.rows(basket).values)`` accumulated row by row gives.
+        ``weights``: one sequence of finite floats per basket (default 1.0 each); ``names``: the index of the result.  An
+        empty basket scores 0 everywhere.
+
+        -> DataFrame [n_sets x N] float64, columns as the dense frame's; with ``top_k=k`` the long frame (set, rank,
+        neighbor, score) of the k best per basket (score descending, label position ascending), selected on the device,
+        k clamped to N.  ``exclude``: "members" (the basket's own members are no candidates), None, or one sequence of
+        labels per basket that are no candidates instead; a basket with fewer than k candidates gets fewer rows."""
+        from . import _sets
+        solver, j, labels = self._kept(group)
+        index, _ = self._ids(j, labels, [])
+        ptr, ids, w, names, k, excl = _sets.prepare(sets, index, weights=weights, names=names, top_k=top_k,
+                                                    exclude=exclude)
+        who = pd.RangeIndex(ptr.size - 1) if names is None else pd.Index(names)
+        if k is None:
+            return pd.DataFrame(solver.score_sets(j, ptr, ids, w), index=who, columns=index.copy())
+        idx, val = solver.score_sets(j, ptr, ids, w, k, excl)
+        return self._best_frame("set", who, index, idx, val)
+
+    def recommend(self, nodes, k, group=None, exclude_seen=True):
+        """Leg 1 of the update for chosen rows: for each fitted node u of ``group`` the k best of ``(W . S)[u, :]``, the
+        scores of u's neighbours' rows (its in-neighbours for the directed classes; for the bipartite classes the
+        group-2 neighbours of a group-1 node, read from group 2's matrix, and the other way round), every weight
+        ``W[u, .]`` as the fit scaled that row.  The same sum as ``score_sets`` of that basket with those weights.
+        ``exclude_seen``: u's neighbours (and, for the directed classes, u itself) are no candidates.
+
+        -> long frame (node, rank, neighbor, score), blocks in the order of ``nodes``; ``neighbor`` is a node of the
+        group the basket lives in.  A node without neighbours gets no rows."""
+        from . import _foldin, _sets
+        if self._model is None:
+            self._kept(1)                                   # (raises: no kept model, or released)
+        solver, sides = self._model
+        side = _foldin.side_of(len(sides), group)
+        if not isinstance(exclude_seen, bool):
+            raise ValueError(f"exclude_seen must be True or False, not {exclude_seen!r}")
+        j, labels = sides[side]
+        src_j, src_labels = sides[len(sides) - 1 - side]
+        src_index, _ = self._ids(src_j, src_labels, [])
+        k = _sets.check_top_k(k, len(src_index))
+        index, ids = self._ids(j, labels, nodes)
+        spec = solver.specs[side]
+        ptr, members, w, excl = _sets.csr_baskets(spec.csr, spec.rowscale, ids, len(sides) == 1, exclude_seen)
+        idx, val = solver.score_sets(src_j, ptr, members, w, k, excl)
+        return self._best_frame("node", index.take(ids), src_index, idx, val, keep_rows=np.diff(ptr) > 0)
+
     def _all_sides(self, make):
         self._kept(1)
         solver, sides = self._model
