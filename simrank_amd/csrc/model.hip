@@ -83,7 +83,10 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(const void* __restrict__
             if (sc >= 0 && sc < src_cols) {
                 const S x = s[offset_of<SL>(src_stride, sr, sc)];
                 if constexpr (kConvert) {
-                    v[e] = __float2half_rn(x * 16384.0f);
+                    // (a source of -0.0 came out of the conversion as +0.0 on the device: the sign of the stored value
+                    // is the source's, whatever it rounds to)
+                    const unsigned short h = __half_as_ushort(__float2half_rn(x * 16384.0f));
+                    v[e] = __ushort_as_half((unsigned short)(h | ((__float_as_uint(x) >> 16) & 0x8000u)));
                     bad += (__half_as_ushort(v[e]) & 0x7c00u) == 0x7c00u;
                 } else {
                     v[e] = x;

@@ -27,10 +27,10 @@ N = 1100
 UPDATES = 3
 
 
-def fit(cls, df, **kw):
+def fit(cls, df, *args, **kw):
     est = getattr(SRA, cls)()
     with contextlib.redirect_stdout(io.StringIO()):
-        est.fit(df, iterations=UPDATES, eps=1e-30, verbose=False, keep=True, **kw)
+        est.fit(df, *args, iterations=UPDATES, eps=1e-30, verbose=False, keep=True, **kw)
     return est
 
 
@@ -56,12 +56,12 @@ VARIANTS = {
 
 
 @contextlib.contextmanager
-def model_of(cls, df, variant, tmp_path, **more):
+def model_of(cls, df, variant, tmp_path, *args, **more):
     kw, then = VARIANTS[variant]
     kw = dict(kw, **more)
     if "world" in kw:
         kw.update(world=LocalWorld(kw["world"]), mode="sparse")
-    model = fit(cls, df, **kw)
+    model = fit(cls, df, *args, **kw)
     try:
         if then == "compact":
             model.compact()
@@ -125,12 +125,32 @@ def check_score_sets(model, frame, group=None):
     assert model.score_sets([], **kw).shape == (0, n) and len(model.score_sets([], top_k=3, **kw)) == 0
 
 
-@pytest.mark.parametrize("variant", list(VARIANTS))
-@pytest.mark.parametrize("cls", ["SimRank", "SimRankPP"])
+# AprioriSimRank with a prior that is NOT symmetric: the kept iterate is asymmetric and dense, so a kernel that read
+# (c, r) for (r, c), or the wrong panel, would not land on the same value
+ASYM_VARIANTS = ("f32-kept", "f32-compact", "fp16-kept", "world3-kept")
+CASES = [(cls, v) for cls in ("SimRank", "SimRankPP") for v in VARIANTS] + [
+    # (fp16-kept refuses an asymmetric prior: the case is named for what it then scores)
+    pytest.param("AprioriSimRank", v, id="AprioriSimRank-fp16-kept-refused-so-f32-compact-fp16") if v == "fp16-kept"
+    else ("AprioriSimRank", v) for v in ASYM_VARIANTS]
+
+
+@pytest.mark.parametrize("cls,variant", CASES)
 def test_score_sets_is_the_statement(cls, variant, graph, tmp_path):
-    with model_of(cls, graph, variant, tmp_path) as model:
+    args = ()
+    if cls == "AprioriSimRank":
+        args = (np.random.default_rng(5).random((N, N)) * 0.5,)
+    if cls == "AprioriSimRank" and variant == "fp16-kept":
+        # a fit that holds its matrices in fp16 takes symmetric priors only (estimators.py says so): the asymmetric
+        # fp16-held iterate is the f32 fit's, narrowed by compact(precision="fp16")
+        with pytest.raises(ValueError, match="symmetric priors only"):
+            fit(cls, graph, *args, storage_precision="fp16")
+        variant = "f32-compact-fp16"
+    with model_of(cls, graph, variant, tmp_path, *args) as model:
         frame = model.frame()
-        assert (frame.values == 0).mean() > 0.5                           # most of S is exactly 0: ties everywhere
+        if cls == "AprioriSimRank":
+            assert not np.array_equal(frame.values, frame.values.T)       # the iterate is not symmetric
+        else:
+            assert (frame.values == 0).mean() > 0.5                       # most of S is exactly 0: ties everywhere
         check_score_sets(model, frame)
 
 
