@@ -277,6 +277,7 @@ FORMAT_VERSION = 1
 _PREFIX = struct.Struct("<8sIQ")
 _ALIGN = 64
 _DTYPES = {"<f2", "<f4", "<f8", "<i4"}
+FORMS = ("dense", "neighbors")      # header "form": one packed matrix per side (the default), or per-node neighbour lists
 CLASSES = ("SimRank", "SimRankPP", "AprioriSimRank", "BipartiteSimRank", "BipartiteSimRankPP", "BipartitleAprioriSimRank")
 
 
@@ -395,6 +396,9 @@ def check_meta(meta, arrays):
         raise ValueError(f"the file names an unknown class {cls!r}")
     if storage not in STORAGES:
         raise ValueError(f"the file names an unknown storage {storage!r}")
+    form = meta.get("form", "dense")                       # (a file from before the neighbour-list form names none)
+    if form not in FORMS:
+        raise ValueError(f"the file names an unknown form {form!r}")
     if not isinstance(sides, list) or len(sides) != (2 if "ipartit" in cls else 1):
         raise ValueError(f"{cls} has {2 if 'ipartit' in cls else 1} side(s); the file describes {len(sides) if isinstance(sides, list) else sides!r}")
     for j, s in enumerate(sides):
@@ -404,15 +408,26 @@ def check_meta(meta, arrays):
             labels, kind = s["labels"], s["label_kind"]
         except (KeyError, TypeError, ValueError) as e:
             raise ValueError(f"side {j} of the header is malformed: {e}") from e
-        layout, stride, nbytes = block_shape(storage, n) if n >= 0 else (None, None, None)
-        if n < 0 or n_src < 0 or nnz < 0 or s.get("layout") != layout or s.get("stride") != stride:
-            raise ValueError(f"side {j}: layout {s.get('layout')} / stride {s.get('stride')} / sizes disagree with {n} nodes "
-                             f"held as {storage}")
+        if n < 0 or n_src < 0 or nnz < 0:
+            raise ValueError(f"side {j}: negative sizes")
         if not isinstance(labels, list) or len(labels) != n:
             raise ValueError(f"side {j}: {len(labels) if isinstance(labels, list) else 'no'} labels for {n} nodes")
         decode_labels(labels[:0], kind)
-        dtype = STORAGES[storage][1].str
-        _expect(arrays, f"iterate{j}", dtype, [nbytes // np.dtype(dtype).itemsize])
+        if form == "neighbors":
+            from ._neighbors import MAX_K, clamp_k
+            k = s.get("k")
+            if type(k) is not int or k < 1 or k > MAX_K or k != clamp_k(k, n):
+                raise ValueError(f"side {j}: k = {k!r} kept neighbours disagree with {n} nodes (at most {MAX_K})")
+            _expect(arrays, f"nbr_ids{j}", "<i4", [n, k])
+            _expect(arrays, f"nbr_vals{j}", "<f8", [n, k])
+            _expect(arrays, f"diag{j}", "<f8", [n])
+        else:
+            layout, stride, nbytes = block_shape(storage, n)
+            if s.get("layout") != layout or s.get("stride") != stride:
+                raise ValueError(f"side {j}: layout {s.get('layout')} / stride {s.get('stride')} / sizes disagree with {n} "
+                                 f"nodes held as {storage}")
+            dtype = STORAGES[storage][1].str
+            _expect(arrays, f"iterate{j}", dtype, [nbytes // np.dtype(dtype).itemsize])
         _expect(arrays, f"rowptr{j}", "<i4", [n + 1])
         _expect(arrays, f"col{j}", "<i4", [nnz])
         _expect(arrays, f"rowscale{j}", "<f8", [n])
@@ -422,31 +437,49 @@ def check_meta(meta, arrays):
         raise ValueError("the side's pattern is not square")
 
 
-def save(path, solver: DetachedSolver, meta: dict, labels):
-    """Write ``solver`` (detached) to ``path``: ``meta`` = class, weighted, strict; ``labels`` one list per side.  The
-    blocks come from the device in bands of at most ``BAND_BYTES``."""
+def save(path, solver, meta: dict, labels):
+    """Write ``solver`` (a ``DetachedSolver``, or the ``_neighbors.NeighborSolver`` of a pruned model) to ``path``:
+    ``meta`` = class, weighted, strict; ``labels`` one list per side.  The blocks come from the device in bands of at most
+    ``BAND_BYTES``; a pruned model's tables, which are small, in one copy each."""
     ops = solver.ops[0]
+    pruned = not isinstance(solver, DetachedSolver)
     sides, arrays, host = [], [], {}
-    for j, (b, s) in enumerate(zip(solver.blocks, solver.specs)):
+    for j, s in enumerate(solver.specs):
         items, kind = encode_labels(labels[j])
         csr = s.csr
-        sides.append(dict(n=b.n, n_src=int(csr.n_cols), nnz=int(csr.nnz), layout=b.layout, stride=b.stride, C=float(s.coef),
-                          lbd=float(s.lbd), evidence=s.evidence_from is not None, prior=s.apriori is not None,
-                          labels=items, label_kind=kind))
-        dtype = STORAGES[b.storage][1]
-        arrays.append((f"iterate{j}", dtype.str, [b.nbytes // dtype.itemsize]))
+        side = dict(n=solver.n[j], n_src=int(csr.n_cols), nnz=int(csr.nnz), C=float(s.coef),
+                    lbd=float(s.lbd), evidence=s.evidence_from is not None, prior=s.apriori is not None,
+                    labels=items, label_kind=kind)
+        if pruned:
+            t = solver.tables[j]
+            side["k"] = t.k
+            ids, vals, diag = t.host()
+            host[f"nbr_ids{j}"] = np.ascontiguousarray(ids, dtype="<i4")
+            host[f"nbr_vals{j}"] = np.ascontiguousarray(vals, dtype="<f8")
+            host[f"diag{j}"] = np.ascontiguousarray(diag, dtype="<f8")
+            for name in (f"nbr_ids{j}", f"nbr_vals{j}", f"diag{j}"):
+                arrays.append((name, host[name].dtype.str, list(host[name].shape)))
+        else:
+            b = solver.blocks[j]
+            side.update(layout=b.layout, stride=b.stride)
+            dtype = STORAGES[b.storage][1]
+            arrays.append((f"iterate{j}", dtype.str, [b.nbytes // dtype.itemsize]))
+        sides.append(side)
         host[f"rowptr{j}"] = np.ascontiguousarray(csr.rowptr, dtype="<i4")
         host[f"col{j}"] = np.ascontiguousarray(csr.col, dtype="<i4")
         host[f"rowscale{j}"] = np.ascontiguousarray(s.rowscale, dtype="<f8")
         for name in (f"rowptr{j}", f"col{j}", f"rowscale{j}"):
             arrays.append((name, host[name].dtype.str, list(host[name].shape)))
     full = dict(meta, storage=solver.storage, sides=sides)
+    if pruned:
+        full["form"] = "neighbors"
+    blocks = [] if pruned else solver.blocks
     tmp = f"{os.fspath(path)}.part"
-    stage = np.empty(min(BAND_BYTES, max((b.nbytes for b in solver.blocks), default=0)), dtype=np.uint8)
+    stage = np.empty(min(BAND_BYTES, max((b.nbytes for b in blocks), default=0)), dtype=np.uint8)
     try:
         with open(tmp, "wb") as f:
             where = write_header(f, full, arrays)
-            for j, b in enumerate(solver.blocks):
+            for j, b in enumerate(blocks):
                 f.seek(where[f"iterate{j}"][0])
                 for at in range(0, b.nbytes, BAND_BYTES):
                     m = min(BAND_BYTES, b.nbytes - at)
@@ -466,7 +499,7 @@ def save(path, solver: DetachedSolver, meta: dict, labels):
 
 
 def load_file(path, device=None):
-    """-> (meta, DetachedSolver, [labels per side]) of a saved model.  Everything about the file is checked before the
+    """-> (meta, DetachedSolver or (a pruned model's) NeighborSolver, [labels per side]) of a saved model.  Everything about the file is checked before the
     first device allocation; the blocks go to the device in bands of at most ``BAND_BYTES``."""
     from .driver import SideSpec
     from .ingest import CSR
@@ -501,9 +534,27 @@ def load_file(path, device=None):
                 evidence_from = csrs[0] if (j == 1 and strict) else csrs[j]
             specs.append(SideSpec(csrs[j], scales[j], float(s["C"]), evidence_from=evidence_from,
                                   apriori=_HAS_PRIOR if s["prior"] else None, lbd=float(s["lbd"]), storage=meta["storage"]))
+        tables = None
+        if meta.get("form", "dense") == "neighbors":
+            tables = [tuple(read(f"{name}{j}").reshape(arrays[f"{name}{j}"]["shape"]) for name in ("nbr_ids", "nbr_vals", "diag"))
+                      for j in range(len(specs))]
+            for j, (ids, _, _) in enumerate(tables):
+                if ids.size and (int(ids.min()) < -1 or int(ids.max()) >= int(meta["sides"][j]["n"])):
+                    raise ValueError(f"side {j}: a neighbour id outside the {meta['sides'][j]['n']} nodes")
         # ---- the device from here on ----
         from .estimators import _default_ops_factory
         ops = _default_ops_factory(device)(0)
+        if tables is not None:
+            from ._neighbors import NeighborSolver, Tables
+            made = []
+            try:
+                for ids, vals, diag in tables:
+                    made.append(Tables.from_host(ops, ids, vals, diag))
+            except BaseException:
+                for t in made:
+                    t.free()
+                raise
+            return meta, NeighborSolver(ops, specs, made, storage=meta["storage"]), labels
         blocks = []
         try:
             stage = np.empty(min(BAND_BYTES, max((arrays[f"iterate{j}"]["nbytes"] for j in range(len(specs))), default=0)),

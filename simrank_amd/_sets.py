@@ -153,7 +153,8 @@ def _block_exclusions(excl, ids_sorted, whole):
 
 def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
     """Score the baskets (``ptr`` int64 [n_sets + 1], ``ids`` int32 caller ids, ``w`` float64) on ``reader``'s iterate
-    (``_query.Reader``) -> float64 [n_sets, n] in the caller's column order, or with ``k`` (ids int32 [n_sets, k], values
+    (``_query.Reader``, or the ``_neighbors.NeighborReader`` of a pruned model, whose ``score_band`` fills the band from
+    the neighbour lists instead) -> float64 [n_sets, n] in the caller's column order, or with ``k`` (ids int32 [n_sets, k], values
     float64 [n_sets, k]): the k best per basket (score descending, id ascending; id -1 / value 0 past the candidates),
     ``excl`` = (ptr, ids) of the caller ids that are no candidates.  One band of baskets holds at most
     ``_query.SLAB_BYTES`` on the device; per band one score kernel per column block, then one copy of the band or one
@@ -174,6 +175,7 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
     per_basket = max(8, -(-max(b["cols"] for b in reader.blocks) // CHUNK) + 7)
     band = int(max(1, min(n_sets, _query.SLAB_BYTES // (8 * n), MAX_BLOCKS // per_basket)))
     whole = len(reader.blocks) == 1
+    score_band = getattr(reader, "score_band", None)
     held = []
 
     def put(host):
@@ -218,9 +220,13 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
                 if not cols:
                     continue
                 piece = slab + 8 * off
-                stage("score_ms", lambda: check(lib.simrank_sets_score(
-                    b["ptr"], b["layout"], b["stride"], b["rows"], cols, cmap, cols, ptr_dev + 8 * q0, pos_dev, w_dev, m,
-                    None if xp is None else xp + 8 * q0, xc, piece, cols, order, ops.stream), "simrank_sets_score"))
+                if score_band is not None:               # (a pruned model: the same band from its neighbour lists)
+                    stage("score_ms", lambda: score_band(ptr_dev + 8 * q0, pos_dev, w_dev, m,
+                                                         None if xp is None else xp + 8 * q0, xc, piece, cols))
+                else:
+                    stage("score_ms", lambda: check(lib.simrank_sets_score(
+                        b["ptr"], b["layout"], b["stride"], b["rows"], cols, cmap, cols, ptr_dev + 8 * q0, pos_dev, w_dev, m,
+                        None if xp is None else xp + 8 * q0, xc, piece, cols, order, ops.stream), "simrank_sets_score"))
                 if k is not None:
                     kk = kks[i]
                     stage("topk_ms", lambda: check(lib.simrank_sets_topk(

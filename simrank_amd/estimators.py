@@ -352,6 +352,7 @@ class _KeptModel:
         from ._query import check_k
         k = check_k(k)
         solver, j, labels = self._kept(group)
+        self._check_kept_neighbors(solver, [j], k)
         lab, ids = self._ids(j, labels, nodes)
         idx, val = solver.topk_of(j, ids, k)
         n, kk = idx.shape
@@ -386,6 +387,9 @@ class _KeptModel:
         if self._model is None:
             self._kept(1)                                   # (raises: no kept model, or released)
         solver, sides = self._model
+        if self.kept_neighbors is not None:
+            raise ValueError("fold_in needs whole rows of the iterate, which a pruned model no longer holds: fold in "
+                             "before prune()")
         side = _foldin.side_of(len(sides), group)
         specs = getattr(solver, "specs", None)
         strict = bool(specs and len(specs) == 2 and specs[1].evidence_from is not None
@@ -490,6 +494,8 @@ class _KeptModel:
         """What ``fit(top_k=k)`` returns."""
         from ._query import check_k
         k = check_k(k)
+        if self._model is not None:
+            self._check_kept_neighbors(self._model[0], [j for j, _ in self._model[1]], k)
         return self._all_sides(lambda solver, j, lab: _topk_frame(solver, j, k, lab))
 
     def pairs(self, min_similarity, max_pairs=2 ** 27):
@@ -505,12 +511,18 @@ class _KeptModel:
         in binary16, round to nearest even: relative error <= 2^-11 down to 2^-28, absolute <= 2^-39 below), a ValueError
         that names the count, with the model left as it was, when a value does not fit, and a ValueError before any device
         work on a float64 model.  Peak device memory during the call is the plan plus the copy; afterwards N^2 x (4 | 2 |
-        8) bytes per side plus, once ``fold_in`` ran, the side's CSR.  Idempotent; returns the estimator."""
+        8) bytes per side plus, once ``fold_in`` ran, the side's CSR.  Idempotent; returns the estimator.  A pruned model
+        (``prune``) is returned unchanged; narrowing one is a ValueError."""
         from . import _model
         _model.check_precision(precision)
         if self._model is None:
             self._kept(1)                                   # (raises: no kept model, or released)
         solver, sides = self._model
+        if self.kept_neighbors is not None:
+            if precision is not None:
+                raise ValueError("compact(precision='fp16') narrows a model's matrix; a pruned model holds float64 "
+                                 "neighbour lists and no matrix")
+            return self
         if isinstance(solver, _model.DetachedSolver) and (precision is None or solver.storage == "fp16"):
             return self
         detached = _model.detach(solver, precision)         # (raises with the kept model intact)
@@ -518,15 +530,74 @@ class _KeptModel:
         solver.release()
         return self
 
+    def prune(self, k):
+        """Keep, for every node of every group, its ``k`` most similar OTHER nodes and the diagonal element, and release
+        the model's matrices (the evidence counts stay, as after ``compact``): N x k x 12 + N x 8 bytes per side instead
+        of N^2 x (4 | 2 | 8).  The kept entries are chosen in the total order (value descending, label position
+        ascending; -0.0 and +0.0 tie, NaN is never kept; exact zeros count where they fall inside the first k): exactly
+        the entries, in the order, that ``most_similar([a], k)`` returned before.  ``k`` is clamped to N - 1 per group.
+        Values are stored widened to float64, as every query returns them.
+
+        From then on every query answers for the matrix P that holds the kept entries, the diagonal and +0.0 everywhere
+        else, bit for bit as the same query would on a dense model holding P: ``frame``, ``rows``, ``similarity``,
+        ``pairs``, ``score_sets`` and ``recommend``; ``most_similar(nodes, k2)`` and ``top_k(k2)`` with ``k2 <= k`` return
+        what the unpruned model returned (``k2 > k`` is a ValueError).  P is in general NOT symmetric: ``similarity(a, b)``
+        reads a's list, so b may be among a's k best while a is not among b's.  ``fold_in`` needs whole rows and is a
+        ValueError: fold in before pruning.  ``save`` writes the lists; ``load_model`` reads them back.
+
+        Works on a kept, a compact and a loaded model; a model held in several column blocks (``LocalWorld(P)``) is packed
+        into one temporary block first (peak memory: the plan plus that copy).  On a pruned model ``k`` at most
+        ``kept_neighbors`` cuts the lists, a larger one is a ValueError.  Every refusal comes before any device work.
+        Returns the estimator."""
+        from . import _neighbors
+        if self._model is None:
+            from ._query import check_k
+            check_k(k)
+            self._kept(1)                                   # (raises: no kept model, or released)
+        solver, sides = self._model
+        k = _neighbors.check_prune_k(k, solver.n)
+        if isinstance(solver, _neighbors.NeighborSolver):
+            self._check_kept_neighbors(solver, range(len(solver.n)), k)
+            if all(_neighbors.clamp_k(k, n) == kk for n, kk in zip(solver.n, solver.kept_k)):
+                return self
+            pruned = solver.truncated(k)
+        else:
+            pruned = _neighbors.prune(solver, k)            # (raises with the kept model intact)
+        self._model = (pruned, sides)
+        solver.release()
+        return self
+
+    @staticmethod
+    def _check_kept_neighbors(solver, js, k):
+        """ValueError when ``k`` (as the queries clamp it) asks a pruned model for more than it keeps."""
+        kept = getattr(solver, "kept_k", None)
+        if isinstance(kept, list):
+            for j in js:
+                if min(k, max(1, solver.n[j] - 1)) > kept[j]:
+                    raise ValueError(f"this model was pruned to kept_neighbors = {kept[j]} neighbours per node: k = {k} asks "
+                                     f"for more than it keeps")
+
+    @property
+    def kept_neighbors(self):
+        """k of ``prune(k)`` (as clamped; a tuple of two where the two groups of a bipartite model were clamped
+        differently), or None on a model that was not pruned."""
+        if self._model is None:
+            return None
+        kept = getattr(self._model[0], "kept_k", None)
+        if not isinstance(kept, list):
+            return None
+        return kept[0] if len(set(kept)) == 1 else tuple(kept)
+
     @property
     def device_bytes(self):
         """Bytes of device memory in the model's own matrices: the packed blocks of a compact model; of a model that still
-        holds its plan, the iterates the queries read (the plan holds more: see ``compact``)."""
+        holds its plan, the iterates the queries read (the plan holds more: see ``compact``); the neighbour lists of a pruned
+        model (N x k x 12 + N x 8 per side)."""
         from . import _model
         if self._model is None:
             self._kept(1)
         solver, sides = self._model
-        if isinstance(solver, _model.DetachedSolver):
+        if isinstance(solver, _model.DetachedSolver) or self.kept_neighbors is not None:
             return solver.device_bytes
         return sum(_model.block_bytes(b) for j, _ in sides for b in solver._reader(j).blocks)
 
@@ -534,7 +605,8 @@ class _KeptModel:
         """Write the model to one file ``load_model`` reads back (a JSON header, then raw little-endian arrays: the packed
         iterates, the CSR and the row scales; no pickle).  A model that still holds its plan is packed into a temporary
         block first and stays as it is.  Labels must be Python ``int`` (any size) or ``str``, or the integers of one NumPy
-        integer type; anything else is a ValueError that names the type."""
+        integer type; anything else is a ValueError that names the type.  A pruned model writes its neighbour lists
+        instead of the iterates (header "form": "neighbors"; the format version is the same)."""
         from . import _model
         if self._model is None:
             self._kept(1)
@@ -547,7 +619,7 @@ class _KeptModel:
                 "strict": bool(len(specs) == 2 and specs[1].evidence_from is not None
                                and specs[1].evidence_from is specs[0].csr),
                 "converged_at": getattr(self, "converged_at", None), "engine_mode": getattr(self, "engine_mode", None)}
-        if isinstance(solver, _model.DetachedSolver):
+        if isinstance(solver, _model.DetachedSolver) or self.kept_neighbors is not None:
             _model.save(path, solver, meta, labels)
             return
         temp = _model.detach(solver)
