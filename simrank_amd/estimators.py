@@ -503,6 +503,29 @@ class _KeptModel:
         _check_pairs_args(min_similarity, max_pairs)
         return self._all_sides(lambda solver, j, lab: _pairs_frame(solver, j, min_similarity, max_pairs, lab))
 
+    def count_pairs(self, thresholds):
+        """int64 array, one entry per threshold in the order given: the number of ordered pairs (a, b) of different nodes
+        with ``S[a, b] >= t``, compared in float64 on the bits the dense frame holds: for t > 0 the number of rows
+        ``pairs(t)`` returns.  ``thresholds``: 1 to 1024 finite numbers of any sign, in any order, repeats allowed.  NaN
+        never counts; -0.0 >= 0.0 does.  One sweep of the iterate in place on the device (libsimrank_profile.so); nothing
+        but the counts crosses.  A pruned model is counted on the host from its lists, the absent +0.0 entries added by
+        arithmetic.  A tuple of two for the bipartite classes."""
+        from . import _profile
+        ts = _profile.check_thresholds(thresholds)
+        return self._all_sides(lambda solver, j, lab: _profile.count_pairs(solver, j, ts))
+
+    def threshold_for(self, max_pairs):
+        """``(t, n)``: the smallest value ``t`` (float64) occurring off the diagonal whose count ``n`` of pairs with
+        ``S[a, b] >= t`` is at most ``max_pairs`` (an int >= 1): ``pairs(t, max_pairs=max_pairs)`` then succeeds with
+        exactly ``n`` rows when t > 0.  Equal values stay together: when the ``max_pairs``-th and the next largest value
+        are equal, ``t`` is the next larger distinct value.  ``(inf, 0)`` when even the largest value occurs more often,
+        or there is no pair.  -0.0 and +0.0 are one value, reported as +0.0; NaN is ignored.  A radix select over the
+        iterate in place: 3 sweeps of an f32 model, 2 of an fp16-held and 6 of a float64 one, whatever N and
+        ``max_pairs``.  A tuple of two for the bipartite classes."""
+        from . import _profile
+        m = _profile.check_max_pairs(max_pairs)
+        return self._all_sides(lambda solver, j, lab: _profile.threshold_for(solver, j, m))
+
     def compact(self, precision=None):
         """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense
         frame's order (libsimrank_model.so), then the plan's matrices are released (the evidence counts stay, so the lazy
