@@ -526,6 +526,28 @@ class _KeptModel:
         m = _profile.check_max_pairs(max_pairs)
         return self._all_sides(lambda solver, j, lab: _profile.threshold_for(solver, j, m))
 
+    def components(self, t):
+        """Single-linkage clusters at threshold ``t``: the connected components of the graph that joins two different
+        nodes a, b iff ``S[a, b] >= t`` or ``S[b, a] >= t``, the comparison ``pairs`` and ``count_pairs`` make (float64 on
+        the bits the dense frame holds; NaN never joins, -0.0 >= 0.0 does): iff (a, b) or (b, a) is a row of ``pairs(t)``.
+        ``t``: one finite number -> a Series "component" (int64) over the dense frame's labels in its order; a sequence
+        of 1 to 8 numbers of any sign, in any order, repeats allowed -> a DataFrame with one such column per threshold,
+        labelled ``float(t)``, in the order given.  Components are numbered 0, 1, 2, ... in the order of their first
+        member in the frame's order, whatever the device did.  One sweep of the iterate in place for all thresholds
+        (libsimrank_cluster.so: a lock-free union-find on integer atomics); N labels per threshold cross.  A pruned
+        model is answered on the host for its matrix P, whose absent entries are +0.0: at t <= 0 they join their pairs.
+        A tuple of two for the bipartite classes."""
+        from . import _cluster
+        ts, scalar = _cluster.check_thresholds(t)
+
+        def make(solver, j, lab):
+            labels = _cluster.number(_cluster.roots(solver, j, ts))
+            index = pd.Index(lab)
+            if scalar:
+                return pd.Series(labels[0], index=index, name="component", dtype=np.int64)
+            return pd.DataFrame(labels.T.reshape(len(index), len(ts)), index=index, columns=[float(x) for x in ts], dtype=np.int64)
+        return self._all_sides(make)
+
     def compact(self, precision=None):
         """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense
         frame's order (libsimrank_model.so), then the plan's matrices are released (the evidence counts stay, so the lazy
