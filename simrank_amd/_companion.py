@@ -1,6 +1,7 @@
-"""What the ctypes bindings of the companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``) share: where
-libsimrank_NAME.so and include/simrank_NAME.h lie, the lazy load with the version check, and ``check``.  A binding keeps
-its prototypes, structures and host helpers.  No CPU fallback: a missing library is an error.
+"""What the ctypes bindings of the nine companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
+``_sets``, ``_neighbors``, ``_profile``, ``_cluster``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
+the lazy load with the version check, ``check``, and the layout codes of a block of an iterate.  A binding keeps its
+prototypes, structures and host helpers.  No CPU fallback: a missing library is an error.
 """
 from __future__ import annotations
 
@@ -9,8 +10,8 @@ import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
-# the layouts of a block of an iterate ("iterate_layout" of simrank_plan_get & co): one set of codes for the select,
-# query and fold-in libraries (csrc/companion.h asserts it of their headers)
+# the layouts of a block of an iterate ("iterate_layout" of simrank_plan_get & co): one set of codes for every library
+# that reads one, all but f64 (csrc/companion.h asserts it of their headers)
 PANEL_F32, ROWMAJOR_F32, PANEL_F16, ROWMAJOR_F64 = 0, 1, 2, 3
 
 

@@ -1,11 +1,10 @@
 // Single-linkage clusters of an iterate that stays on the device (include/simrank_cluster.h, libsimrank_cluster.so): the
 // connected components of "S[a][b] >= t or S[b][a] >= t" for up to 8 thresholds in one sweep of the matrix.
 //
-// The sweep is profile.hip's (the library stands alone, so the walk is written out again here): panel layouts give a wave
-// EIGHT consecutive rows (lane group g = lane >> 3 owns row 8 w + g, lane q = lane & 7 the 16 bytes at 16 q of every
-// panel's row segment), the row-major layouts give it one row (16 bytes per lane).  Every entry that passes a level's
-// threshold is an edge (row node, column node) of that level's graph; the graph lives in a forest parent[level][node]
-// with parent[x] <= x always.
+// The sweep is the walk that select.hip and profile.hip share (companion.h: eight rows per wave on panels, one on a
+// row-major block, 16-byte loads; only what is done with a loaded piece is written here).  Every entry that passes a
+// level's threshold is an edge (row node, column node) of that level's graph; the graph lives in a forest
+// parent[level][node] with parent[x] <= x always.
 //
 // What an edge costs.  At a low threshold nearly every entry is an edge and at most n - 1 of them change anything, so an
 // entry first reads its column node's parent and compares it with a member of the row's component that the lane keeps in
@@ -37,11 +36,9 @@ COMPANION_SAME_LAYOUT(SIMRANK_CLUSTER_, ROWMAJOR_F32);
 COMPANION_SAME_LAYOUT(SIMRANK_CLUSTER_, PANEL_F16);
 COMPANION_SAME_LAYOUT(SIMRANK_CLUSTER_, ROWMAJOR_F64);
 
-typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
-
 constexpr int kMaxLevels = SIMRANK_CLUSTER_MAX_LEVELS;
-constexpr int kThreads = 256;
-constexpr int kMaxGrid = 256 * 8;
+constexpr int kThreads = kSweepThreads;
+constexpr int kMaxGrid = kSweepMaxGrid;
 constexpr unsigned kCapSlack = 8;
 
 // ---- the forest ----------------------------------------------------------------------------------------------------------
@@ -97,27 +94,6 @@ __device__ inline int32_t unite(int32_t* P, int32_t a, int32_t b, unsigned cap, 
     return -1;
 }
 
-// ---- what a layout's element is (profile.hip's) --------------------------------------------------------------------------
-template <int LAYOUT>
-struct Elem {
-    static constexpr bool ROWMAJOR = LAYOUT == ROWMAJOR_F32 || LAYOUT == ROWMAJOR_F64;
-    static constexpr int V = LAYOUT == PANEL_F16 ? 8 : LAYOUT == ROWMAJOR_F64 ? 2 : 4;   // values per 16-byte load
-    static constexpr int L = ROWMAJOR ? 64 : 8;                                          // lanes per row
-    using Cmp = typename std::conditional<LAYOUT == ROWMAJOR_F64, double, float>::type;  // compared as
-
-    // value i of a 16-byte piece, as the dense hand-back widens it (fp16 -> f32 is exact, x 2^-14 is exact)
-    __device__ static Cmp value(const v4u32& x, int i) {
-        if constexpr (LAYOUT == ROWMAJOR_F64) {
-            return __longlong_as_double((long long)((uint64_t(x[2 * i + 1]) << 32) | x[2 * i]));
-        } else if constexpr (LAYOUT == PANEL_F16) {
-            const unsigned short h = (unsigned short)((x[i >> 1] >> (16 * (i & 1))) & 0xffffu);
-            return float(__builtin_bit_cast(_Float16, h)) * kHalfScale;
-        } else {
-            return __uint_as_float(x[i]);
-        }
-    }
-};
-
 // ---- the sweep -----------------------------------------------------------------------------------------------------------
 template <int LAYOUT>
 __global__ __launch_bounds__(kThreads) void union_kernel(const void* __restrict__ S, int64_t stride, int64_t n_rows,
@@ -128,14 +104,7 @@ __global__ __launch_bounds__(kThreads) void union_kernel(const void* __restrict_
                                                          int vec) {
     using E = Elem<LAYOUT>;
     using Cmp = typename E::Cmp;
-    constexpr int V = E::V, L = E::L;
-    constexpr int R = 64 / L;                    // rows per wave
-    constexpr int W = L * V;                     // columns per chunk: a panel, or 64 x V columns of a row
-    constexpr int U = 4;                         // chunks in flight
-    const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
-    const int64_t wave = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
-    const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
-    const int64_t n_chunks = (n_cols + W - 1) / W;
+    WALK_GEOMETRY(LAYOUT, n_cols);
     const unsigned cap = unsigned(n) + kCapSlack;
     unsigned bad = 0;
 
@@ -186,27 +155,7 @@ __global__ __launch_bounds__(kThreads) void union_kernel(const void* __restrict_
 #pragma unroll
         for (int l = 0; l < kMaxLevels; ++l) mine[l] = rid;
         for (int64_t k0 = 0; k0 < n_chunks; k0 += U) {
-            v4u32 x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t k = k0 + u;
-                x[u] = v4u32{0, 0, 0, 0};
-                if (!live || k >= n_chunks) continue;
-                if constexpr (!E::ROWMAJOR) {
-                    x[u] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(S) + ((k * stride + r) * 8 + q));
-                } else {
-                    constexpr int D = 4 / V;     // dwords per value
-                    const unsigned* row = reinterpret_cast<const unsigned*>(S) + r * stride * D;
-                    const int64_t c0 = k * W + int64_t(V) * q;
-                    if (vec && c0 + V - 1 < n_cols) {
-                        x[u] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(row + c0 * D));
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (c0 + i / D < n_cols) x[u][i] = row[c0 * D + i];
-                    }
-                }
-            }
+            WALK_LOAD(LAYOUT, x, S, stride, r, live, k0, n_cols, vec)
             // One 16-byte piece at a time, as a loop: the slow path below then exists once per level, not once per value
             // in flight.
 #pragma unroll 1
@@ -219,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void union_kernel(const void* __restrict_
                 unsigned ok = 0;                                         // bit i: value i is an entry between two nodes
 #pragma unroll
                 for (int i = 0; i < V; ++i) {
-                    v[i] = E::value(xu, i);
+                    v[i] = E::value(E::raw(xu, i));
                     cid[i] = 0;
                     if (row_ok && c0 + i < n_cols) {
                         cid[i] = col_ids ? col_ids[c0 + i] : int32_t(c0 + i);
@@ -281,30 +230,6 @@ int flat_grid(int64_t total) {
     return (int)std::max<int64_t>(1, std::min<int64_t>((total + kThreads - 1) / kThreads, kMaxGrid));
 }
 
-struct Launch {
-    int grid, vec;
-};
-
-int plan_launch(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, Launch* out) {
-    REQUIRE(layout >= PANEL_F32 && layout <= ROWMAJOR_F64, "unknown layout %d", (int)layout);
-    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_cols < (int64_t(1) << 31) && n_rows < (int64_t(1) << 31),
-            "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    REQUIRE(n_rows == 0 || n_cols == 0 || S, "S is NULL");
-    const bool rowmajor = layout == ROWMAJOR_F32 || layout == ROWMAJOR_F64;
-    REQUIRE(rowmajor ? stride >= n_cols : stride >= n_rows, "stride %lld is too small for %lld x %lld", (long long)stride,
-            (long long)n_rows, (long long)n_cols);
-    const bool aligned = (reinterpret_cast<uintptr_t>(S) & 15) == 0;
-    REQUIRE(rowmajor || aligned, "a panel-blocked block must be 16-byte aligned");
-    REQUIRE(layout != ROWMAJOR_F64 || (reinterpret_cast<uintptr_t>(S) & 7) == 0, "a float64 block must be 8-byte aligned");
-    REQUIRE(layout != ROWMAJOR_F32 || (reinterpret_cast<uintptr_t>(S) & 3) == 0, "an f32 block must be 4-byte aligned");
-    const int64_t rows_per_wave = rowmajor ? 1 : 8;
-    const int64_t waves = std::max<int64_t>(1, (n_rows + rows_per_wave - 1) / rows_per_wave);
-    const int64_t per_group = kThreads / 64;
-    out->grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + per_group - 1) / per_group, kMaxGrid));
-    out->vec = rowmajor && aligned && (stride % (layout == ROWMAJOR_F64 ? 2 : 4)) == 0;
-    return SIMRANK_CLUSTER_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -326,21 +251,18 @@ int simrank_cluster_union(const void* S, int32_t layout, int64_t stride, int64_t
                           const int32_t* row_ids, const int32_t* col_ids, const void* edges, int32_t n_levels,
                           int32_t* parent, int64_t n, int32_t* status, void* stream) {
     Launch l;
-    int rc = plan_launch(S, layout, stride, n_rows, n_cols, &l);
+    int rc = plan_launch(S, layout, stride, n_rows, n_cols, true, &l);
     if (rc) return rc;
     rc = check_forest(parent, n, n_levels, status);
     if (rc) return rc;
     REQUIRE(edges, "edges is NULL");
     if (n_rows == 0 || n_cols == 0 || n == 0) return SIMRANK_CLUSTER_OK;
     hipStream_t st = as_stream(stream);
-#define UNION_LAUNCH(LAYOUT)                                                                                            \
-    hipLaunchKernelGGL((union_kernel<LAYOUT>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols, row_ids, \
-                       col_ids, static_cast<const Elem<LAYOUT>::Cmp*>(edges), (int)n_levels, parent, n, status, l.vec)
-    if (layout == PANEL_F32) UNION_LAUNCH(PANEL_F32);
-    else if (layout == ROWMAJOR_F32) UNION_LAUNCH(ROWMAJOR_F32);
-    else if (layout == PANEL_F16) UNION_LAUNCH(PANEL_F16);
-    else UNION_LAUNCH(ROWMAJOR_F64);
-#undef UNION_LAUNCH
+    with_layout(layout, [&](auto L) {
+        hipLaunchKernelGGL((union_kernel<L>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols, row_ids,
+                           col_ids, static_cast<const typename Elem<L>::Cmp*>(edges), (int)n_levels, parent, n, status,
+                           l.vec);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_CLUSTER_OK;
 }

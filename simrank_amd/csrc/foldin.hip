@@ -288,8 +288,6 @@ __global__ __launch_bounds__(32 * kLongHalfWaves) void foldin_apply_long_kernel(
     }
 }
 
-bool known(int32_t layout) { return layout >= SIMRANK_FOLDIN_PANEL_F32 && layout <= SIMRANK_FOLDIN_ROWMAJOR_F64; }
-
 template <int L>
 void launch_gather(bool vec, unsigned grid, hipStream_t st, const void* S, int64_t stride, int64_t n_rows, int64_t n_cols,
                    const int32_t* col_ids, int64_t col_base, const int32_t* list_ptr, const int32_t* list_pos,
@@ -324,7 +322,7 @@ int simrank_foldin_version(void) { return SIMRANK_FOLDIN_VERSION; }
 const char* simrank_foldin_last_error(void) { return g_error.c_str(); }
 
 int64_t simrank_foldin_t_bytes(int32_t layout, int64_t n_src) {
-    if (!known(layout) || n_src < 0) return -1;
+    if (!known_layout(layout) || n_src < 0) return -1;
     return n_src * kTile * int64_t(layout == SIMRANK_FOLDIN_ROWMAJOR_F64 ? sizeof(double) : sizeof(float));
 }
 
@@ -344,12 +342,12 @@ int simrank_foldin_free(void* ptr) {
 int simrank_foldin_gather(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols,
                           const int32_t* col_ids, int64_t col_base, const int32_t* list_ptr, const int32_t* list_pos,
                           const double* w, int32_t n_tile, void* T, int64_t n_src, void* stream) {
-    REQUIRE(known(layout), "unknown layout %d", (int)layout);
+    REQUIRE(known_layout(layout), "unknown layout %d", (int)layout);
     REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
                 "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
     REQUIRE(n_src >= 0 && n_src < (int64_t(1) << 31), "bad number of source nodes %lld", (long long)n_src);
     REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);
-    const bool panels = layout == SIMRANK_FOLDIN_PANEL_F32 || layout == SIMRANK_FOLDIN_PANEL_F16;
+    const bool panels = is_panel(layout);
     REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
                 panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
     REQUIRE(col_ids || (col_base >= 0 && col_base + n_cols <= n_src), "columns %lld .. %lld are not source nodes",
@@ -361,32 +359,11 @@ int simrank_foldin_gather(const void* S, int32_t layout, int64_t stride, int64_t
     const bool base16 = reinterpret_cast<uintptr_t>(S) % 16 == 0;
     REQUIRE(base16 || !panels, "a panel block starts on 16 bytes");
     hipStream_t st = as_stream(stream);
-    switch (layout) {
-        case SIMRANK_FOLDIN_PANEL_F32: {
-            const unsigned grid = (unsigned)((n_cols + 255) / 256);
-            launch_gather<SIMRANK_FOLDIN_PANEL_F32>(true, grid, st, S, stride, n_rows, n_cols, col_ids, col_base, list_ptr,
-                                                    list_pos, w, n_tile, T, n_src);
-            break;
-        }
-        case SIMRANK_FOLDIN_ROWMAJOR_F32: {
-            const unsigned grid = (unsigned)((n_cols + 255) / 256);
-            launch_gather<SIMRANK_FOLDIN_ROWMAJOR_F32>(base16 && stride % 4 == 0, grid, st, S, stride, n_rows, n_cols, col_ids,
-                                                       col_base, list_ptr, list_pos, w, n_tile, T, n_src);
-            break;
-        }
-        case SIMRANK_FOLDIN_PANEL_F16: {
-            const unsigned grid = (unsigned)((n_cols + 255) / 256);
-            launch_gather<SIMRANK_FOLDIN_PANEL_F16>(true, grid, st, S, stride, n_rows, n_cols, col_ids, col_base, list_ptr,
-                                                    list_pos, w, n_tile, T, n_src);
-            break;
-        }
-        default: {
-            const unsigned grid = (unsigned)((n_cols + 127) / 128);
-            launch_gather<SIMRANK_FOLDIN_ROWMAJOR_F64>(base16 && stride % 2 == 0, grid, st, S, stride, n_rows, n_cols, col_ids,
-                                                       col_base, list_ptr, list_pos, w, n_tile, T, n_src);
-            break;
-        }
-    }
+    with_layout(layout, [&](auto L) {
+        constexpr int K = Lay<L>::kCols, BC = 64 * K;                // a lane's run; the columns of one workgroup
+        launch_gather<L>(panels || (base16 && stride % K == 0), (unsigned)((n_cols + BC - 1) / BC), st, S, stride, n_rows,
+                         n_cols, col_ids, col_base, list_ptr, list_pos, w, n_tile, T, n_src);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_FOLDIN_OK;
 }
@@ -412,7 +389,7 @@ int simrank_foldin_apply(const int32_t* rowptr, const int32_t* col, const double
                          const int32_t* long_rows, int64_t n_long, const void* T, int32_t t_layout, const uint32_t* member,
                          double coef, double lbd, const double* prior, int64_t ld_prior, int32_t n_tile, double* out,
                          int64_t ld_out, void* stream) {
-    REQUIRE(known(t_layout), "unknown layout %d", (int)t_layout);
+    REQUIRE(known_layout(t_layout), "unknown layout %d", (int)t_layout);
     REQUIRE(n_out >= 0 && n_out < (int64_t(1) << 31) && n_src >= 0 && n_src < (int64_t(1) << 31),
                 "bad shape %lld x %lld", (long long)n_out, (long long)n_src);
     REQUIRE(n_tile >= 0 && n_tile <= kTile, "n_tile must be in [0, %d] (got %d)", kTile, (int)n_tile);

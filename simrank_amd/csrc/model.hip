@@ -30,22 +30,6 @@ COMPANION_SAME_LAYOUT(SIMRANK_MODEL_, ROWMAJOR_F64);
 constexpr int kThreads = 256;
 constexpr int64_t kMaxBlocks = int64_t(1) << 23;          // x 256 threads = 2^31 work-items per launch
 
-template <int L> struct Stored { using type = float; };
-template <> struct Stored<PANEL_F16> { using type = __half; };
-template <> struct Stored<ROWMAJOR_F64> { using type = double; };
-
-// element offset of (r, c) in layout L
-template <int L>
-__device__ inline int64_t offset_of(int64_t stride, int64_t r, int64_t c) {
-    if constexpr (L == PANEL_F32) {
-        return ((c >> 5) * stride + r) * 32 + (c & 31);
-    } else if constexpr (L == PANEL_F16) {
-        return ((c >> 6) * stride + r) * 64 + (c & 63);
-    } else {
-        return r * stride + c;
-    }
-}
-
 // Block b of a band: label x = b % 8 (the blocks that share an XCD), slot s = b / 8; the slots of a label walk the
 // chunks of the band's rows 8 * (s / chunks) + x, so that every chunk of a destination row runs under the same label.
 template <int SL, int DL>
@@ -118,18 +102,6 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(const void* __restrict__
     }
 }
 
-int check_block(const char* what, const void* p, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols) {
-    REQUIRE(layout >= SIMRANK_MODEL_PANEL_F32 && layout <= SIMRANK_MODEL_ROWMAJOR_F64, "unknown %s layout %d", what,
-            (int)layout);
-    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
-            "bad %s block shape %lld x %lld", what, (long long)n_rows, (long long)n_cols);
-    REQUIRE(p || n_rows == 0 || n_cols == 0, "%s is NULL", what);
-    const bool panels = layout == SIMRANK_MODEL_PANEL_F32 || layout == SIMRANK_MODEL_PANEL_F16;
-    REQUIRE(stride >= (panels ? n_rows : n_cols), "%s stride %lld is smaller than the block's %s (%lld)", what,
-            (long long)stride, panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
-    return SIMRANK_MODEL_OK;
-}
-
 template <int SL, int DL>
 int launch(const void* src, int64_t src_stride, int64_t src_rows, int64_t src_cols, const int32_t* row_map,
            const int32_t* col_dst, const int32_t* col_src, int64_t n_list, void* dst, int64_t dst_stride, int64_t dst_rows,
@@ -163,9 +135,9 @@ int simrank_model_pack(const void* src, int32_t src_layout, int64_t src_stride, 
                        const int32_t* row_map, const int32_t* col_dst, const int32_t* col_src, int64_t n_list, void* dst,
                        int32_t dst_layout, int64_t dst_stride, int64_t dst_rows, int64_t dst_cols, int64_t* overflow,
                        void* stream) {
-    int rc = check_block("source", src, src_layout, src_stride, src_rows, src_cols);
+    int rc = check_block(src, src_layout, src_stride, src_rows, src_cols, "source");
     if (rc) return rc;
-    rc = check_block("destination", dst, dst_layout, dst_stride, dst_rows, dst_cols);
+    rc = check_block(dst, dst_layout, dst_stride, dst_rows, dst_cols, "destination");
     if (rc) return rc;
     REQUIRE(n_list >= 0 && n_list < (int64_t(1) << 29), "bad number of columns %lld", (long long)n_list);
     REQUIRE(row_map || dst_rows <= src_rows, "%lld destination rows exceed the source's %lld and there is no row map",

@@ -64,23 +64,12 @@ __device__ __forceinline__ uint64_t key_of(float v) {      // the same order in 
     return uint64_t((b >> 31) ? ~b : (b | 0x80000000u)) << 32;
 }
 
-// Element (r, c) of a block in layout L: its value key, and the value widened as elem<L> widens it.  The f32 and binary16
+// The width of a layout's value key and the type load<L> (companion.h) hands an element back in.  The f32 and binary16
 // layouts widen exactly and monotonically, so the key of the float orders as the key of the double would.
 template <int L>
 struct Value {
     static constexpr int kKeyBits = (L == ROWMAJOR_F64) ? 64 : 32;
     using Held = typename std::conditional<L == ROWMAJOR_F64, double, float>::type;
-    static __device__ __forceinline__ Held load(const void* __restrict__ S, int64_t stride, int64_t r, int64_t c) {
-        if constexpr (L == PANEL_F32) {
-            return static_cast<const float*>(S)[((c >> 5) * stride + r) * 32 + (c & 31)];
-        } else if constexpr (L == ROWMAJOR_F32) {
-            return static_cast<const float*>(S)[r * stride + c];
-        } else if constexpr (L == PANEL_F16) {
-            return __half2float(static_cast<const __half*>(S)[((c >> 6) * stride + r) * 64 + (c & 63)]) * kHalfScale;
-        } else {
-            return static_cast<const double*>(S)[r * stride + c];
-        }
-    }
 };
 
 // The passes of the radix select: (which key, shift, bits), from the most significant digit down.
@@ -218,7 +207,7 @@ __global__ __launch_bounds__(kThreads) void neighbors_select_kernel(const void* 
                     v[u] = typename V::Held(0);
                     id[u] = self;
                     if (c < cols) {
-                        v[u] = V::load(S, stride, r, c);
+                        v[u] = load<L>(S, stride, r, c);
                         id[u] = col_ids ? col_ids[c] : int(c);
                     }
                 }
@@ -249,7 +238,7 @@ __global__ __launch_bounds__(kThreads) void neighbors_select_kernel(const void* 
                     v[u] = typename V::Held(0);
                     id[u] = self;
                     if (c < cols) {
-                        v[u] = V::load(S, stride, r, c);
+                        v[u] = load<L>(S, stride, r, c);
                         id[u] = col_ids ? col_ids[c] : int(c);
                     }
                 }
@@ -428,18 +417,6 @@ __global__ __launch_bounds__(kThreads) void neighbors_score_kernel(const int32_t
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols) {
-    REQUIRE(layout >= SIMRANK_NEIGHBORS_PANEL_F32 && layout <= SIMRANK_NEIGHBORS_ROWMAJOR_F64, "unknown layout %d",
-            (int)layout);
-    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
-            "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    REQUIRE(S || n_rows == 0 || n_cols == 0, "S is NULL");
-    const bool panels = layout == SIMRANK_NEIGHBORS_PANEL_F32 || layout == SIMRANK_NEIGHBORS_PANEL_F16;
-    REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
-            panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
-    return SIMRANK_NEIGHBORS_OK;
-}
-
 int check_k(int32_t k) {
     REQUIRE(k >= 1 && k <= SIMRANK_NEIGHBORS_MAX_K, "k must be in [1, %d] (got %d)", SIMRANK_NEIGHBORS_MAX_K, (int)k);
     return SIMRANK_NEIGHBORS_OK;
@@ -483,16 +460,10 @@ int simrank_neighbors_select(const void* S, int32_t layout, int64_t stride, int6
     const size_t lds = size_t(cap) * 12 + kBins * sizeof(uint32_t) + sizeof(SelectState);
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)std::min<int64_t>(n_q, int64_t(1) << 20));
-#define NBR_SELECT(L)                                                                                                     \
-    hipLaunchKernelGGL(neighbors_select_kernel<L>, grid, dim3(kThreads), lds, st, S, stride, n_rows, n_cols, row_pos,    \
-                       row_ids, n_q, col_ids, (int)k, cap, idx_out, val_out)
-    switch (layout) {
-        case SIMRANK_NEIGHBORS_PANEL_F32: NBR_SELECT(PANEL_F32); break;
-        case SIMRANK_NEIGHBORS_ROWMAJOR_F32: NBR_SELECT(ROWMAJOR_F32); break;
-        case SIMRANK_NEIGHBORS_PANEL_F16: NBR_SELECT(PANEL_F16); break;
-        default: NBR_SELECT(ROWMAJOR_F64); break;
-    }
-#undef NBR_SELECT
+    with_layout(layout, [&](auto L) {
+        hipLaunchKernelGGL(neighbors_select_kernel<L>, grid, dim3(kThreads), lds, st, S, stride, n_rows, n_cols, row_pos,
+                           row_ids, n_q, col_ids, (int)k, cap, idx_out, val_out);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_NEIGHBORS_OK;
 }

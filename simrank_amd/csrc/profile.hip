@@ -1,13 +1,12 @@
 // The distribution of an iterate that stays on the device (include/simrank_profile.h, libsimrank_profile.so): how many
 // off-diagonal entries lie between sorted thresholds, and one pass of a global radix select on an order-preserving key.
 //
-// Both are one sweep of a block in the layout the plan stores it, with select.hip's row -> wave map and 16-byte loads:
-// panel layouts give a wave EIGHT consecutive rows (lane group g = lane >> 3 owns row 8 w + g, lane q = lane & 7 the 16
-// bytes at 16 q of every panel's row segment), the row-major layouts give it one row (16 bytes per lane, 1 KiB per load
-// instruction).  Every entry becomes a bin number; a workgroup counts bins in 32-bit words of local memory and adds
-// them to the caller's 64-bit counters once, at its end.  A fitted S is mostly exact zeros plus a few repeated values:
-// before the local-memory atomics, up to two rounds of (first pending lane's bin, ballot of the lanes that share it, one
-// add of the popcount by that lane) take the dominant bins out of the way; what is left adds 1 per lane.
+// Both are one sweep of a block in the layout the plan stores it, on the walk that select.hip and cluster.hip share
+// (companion.h: eight rows per wave on panels, one on a row-major block, 16-byte loads).  Every entry becomes a bin
+// number; a workgroup counts bins in 32-bit words of local memory and adds them to the caller's 64-bit counters once, at
+// its end.  A fitted S is mostly exact zeros plus a few repeated values: before the local-memory atomics, up to two
+// rounds of (first pending lane's bin, ballot of the lanes that share it, one add of the popcount by that lane) take the
+// dominant bins out of the way; what is left adds 1 per lane.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -28,12 +27,9 @@ COMPANION_SAME_LAYOUT(SIMRANK_PROFILE_, ROWMAJOR_F32);
 COMPANION_SAME_LAYOUT(SIMRANK_PROFILE_, PANEL_F16);
 COMPANION_SAME_LAYOUT(SIMRANK_PROFILE_, ROWMAJOR_F64);
 
-typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
-
 constexpr int kMaxEdges = SIMRANK_PROFILE_MAX_EDGES;
 constexpr int kMaxBins = 1 << SIMRANK_PROFILE_MAX_DIGIT_BITS;
-constexpr int kThreads = 256;
-constexpr int kMaxGrid = 256 * 8;
+constexpr int kThreads = kSweepThreads;
 
 // ---- keys (host and device) ---------------------------------------------------------------------------------------------
 // sign set: every bit flipped (larger magnitude = smaller key); sign clear: the sign bit set.  -0.0 is keyed as +0.0.
@@ -53,27 +49,12 @@ __host__ __device__ inline uint32_t key16(uint32_t b) {
 }
 __host__ __device__ inline uint32_t unkey16(uint32_t k) { return ((k & 0x8000u) ? (k & 0x7fffu) : ~k) & 0xffffu; }
 
-// ---- what a layout's element is ------------------------------------------------------------------------------------------
+// ---- a layout's element (companion.h) as a key -----------------------------------------------------------------------------
 template <int LAYOUT>
-struct Elem {
-    static constexpr bool ROWMAJOR = LAYOUT == ROWMAJOR_F32 || LAYOUT == ROWMAJOR_F64;
-    static constexpr int V = LAYOUT == PANEL_F16 ? 8 : LAYOUT == ROWMAJOR_F64 ? 2 : 4;   // values per 16-byte load
-    static constexpr int L = ROWMAJOR ? 64 : 8;                                          // lanes per row
+struct Keyed : Elem<LAYOUT> {
+    using Raw = typename Elem<LAYOUT>::Raw;
     static constexpr int KEY_BITS = LAYOUT == PANEL_F16 ? 16 : LAYOUT == ROWMAJOR_F64 ? 64 : 32;
-    using Raw = typename std::conditional<LAYOUT == ROWMAJOR_F64, uint64_t, uint32_t>::type;     // the stored bits
-    using Cmp = typename std::conditional<LAYOUT == ROWMAJOR_F64, double, float>::type;          // compared as
 
-    __device__ static Raw raw(const v4u32& x, int i) {
-        if constexpr (LAYOUT == ROWMAJOR_F64) return (uint64_t(x[2 * i + 1]) << 32) | x[2 * i];
-        else if constexpr (LAYOUT == PANEL_F16) return (x[i >> 1] >> (16 * (i & 1))) & 0xffffu;
-        else return x[i];
-    }
-    // the value as the dense hand-back widens it (fp16 -> f32 is exact, x 2^-14 is exact)
-    __device__ static Cmp value(Raw b) {
-        if constexpr (LAYOUT == ROWMAJOR_F64) return __longlong_as_double((long long)b);
-        else if constexpr (LAYOUT == PANEL_F16) return float(__builtin_bit_cast(_Float16, (unsigned short)b)) * kHalfScale;
-        else return __uint_as_float(b);
-    }
     __device__ static bool is_nan(Raw b) {
         if constexpr (LAYOUT == ROWMAJOR_F64) return (b & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
         else if constexpr (LAYOUT == PANEL_F16) return (b & 0x7fffu) > 0x7c00u;
@@ -110,41 +91,13 @@ __device__ inline void bump(uint32_t* bins, bool in, uint32_t j, int lane) {
 template <int LAYOUT, class Op>
 __device__ inline void sweep(const void* __restrict__ S, int64_t stride, int64_t n_rows, int64_t n_cols,
                              const int32_t* __restrict__ row_ids, const int32_t* __restrict__ col_ids, int vec, Op& op) {
-    using E = Elem<LAYOUT>;
-    constexpr int V = E::V, L = E::L;
-    constexpr int R = 64 / L;                    // rows per wave
-    constexpr int W = L * V;                     // columns per chunk: a panel, or 64 x V columns of a row
-    constexpr int U = 4;                         // chunks in flight
-    const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
-    const int64_t wave = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
-    const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
-    const int64_t n_chunks = (n_cols + W - 1) / W;
+    WALK_GEOMETRY(LAYOUT, n_cols);
     for (int64_t r0 = wave * R; r0 < n_rows; r0 += nwaves * R) {
         const int64_t r = r0 + g;
         const bool live = r < n_rows;
         const int32_t rid = live ? (row_ids ? row_ids[r] : int32_t(r)) : 0;
         for (int64_t k0 = 0; k0 < n_chunks; k0 += U) {
-            v4u32 x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t k = k0 + u;
-                x[u] = v4u32{0, 0, 0, 0};
-                if (!live || k >= n_chunks) continue;
-                if constexpr (!E::ROWMAJOR) {
-                    x[u] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(S) + ((k * stride + r) * 8 + q));
-                } else {
-                    constexpr int D = 4 / V;     // dwords per value
-                    const unsigned* row = reinterpret_cast<const unsigned*>(S) + r * stride * D;
-                    const int64_t c0 = k * W + int64_t(V) * q;
-                    if (vec && c0 + V - 1 < n_cols) {
-                        x[u] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(row + c0 * D));
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (c0 + i / D < n_cols) x[u][i] = row[c0 * D + i];
-                    }
-                }
-            }
+            WALK_LOAD(LAYOUT, x, S, stride, r, live, k0, n_cols, vec)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 if (k0 + u >= n_chunks) break;                           // (wave-uniform)
@@ -153,7 +106,7 @@ __device__ inline void sweep(const void* __restrict__ S, int64_t stride, int64_t
                 for (int i = 0; i < V; ++i) {
                     bool in = live && c0 + i < n_cols;
                     if (in) in = (col_ids ? col_ids[c0 + i] : int32_t(c0 + i)) != rid;
-                    op(in, E::raw(x[u], i));
+                    op(in, Elem<LAYOUT>::raw(x[u], i));
                 }
             }
         }
@@ -176,7 +129,7 @@ __global__ __launch_bounds__(kThreads) void count_kernel(const void* __restrict_
                                                          const typename Elem<LAYOUT>::Cmp* __restrict__ edges_dev,
                                                          int n_edges, int top, unsigned long long* __restrict__ counts,
                                                          int vec) {
-    using E = Elem<LAYOUT>;
+    using E = Keyed<LAYOUT>;
     using Cmp = typename E::Cmp;
     using Raw = typename E::Raw;
     __shared__ Cmp edges[kMaxEdges];
@@ -218,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void digits_kernel(const void* __restrict
                                                           int prefix_bits, int digit_bits,
                                                           unsigned long long* __restrict__ hist,
                                                           unsigned long long* __restrict__ min_above, int vec) {
-    using E = Elem<LAYOUT>;
+    using E = Keyed<LAYOUT>;
     using Raw = typename E::Raw;
     __shared__ uint32_t bins[kMaxBins];
     const int n_bins = 1 << digit_bits;
@@ -254,32 +207,13 @@ __global__ __launch_bounds__(kThreads) void digits_kernel(const void* __restrict
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------
-struct Launch {
-    int grid, vec;
-};
-
-int plan_launch(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, Launch* out) {
-    REQUIRE(layout >= PANEL_F32 && layout <= ROWMAJOR_F64, "unknown layout %d", (int)layout);
-    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_cols < (int64_t(1) << 31) && n_rows < (int64_t(1) << 31),
-            "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    REQUIRE(n_rows == 0 || n_cols == 0 || S, "S is NULL");
-    const bool rowmajor = layout == ROWMAJOR_F32 || layout == ROWMAJOR_F64;
-    REQUIRE(rowmajor ? stride >= n_cols : stride >= n_rows, "stride %lld is too small for %lld x %lld", (long long)stride,
-            (long long)n_rows, (long long)n_cols);
-    const bool aligned = (reinterpret_cast<uintptr_t>(S) & 15) == 0;
-    REQUIRE(rowmajor || aligned, "a panel-blocked block must be 16-byte aligned");
-    REQUIRE(layout != ROWMAJOR_F64 || (reinterpret_cast<uintptr_t>(S) & 7) == 0, "a float64 block must be 8-byte aligned");
-    REQUIRE(layout != ROWMAJOR_F32 || (reinterpret_cast<uintptr_t>(S) & 3) == 0, "an f32 block must be 4-byte aligned");
-    const int64_t rows_per_wave = rowmajor ? 1 : 8;
-    const int64_t waves = std::max<int64_t>(1, (n_rows + rows_per_wave - 1) / rows_per_wave);
-    const int64_t per_group = kThreads / 64;
-    out->grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + per_group - 1) / per_group, kMaxGrid));
-    // a workgroup's bins are 32-bit: it must not see 2^32 entries
-    const int64_t turns = (waves + out->grid * per_group - 1) / (out->grid * per_group);
-    REQUIRE((double)turns * per_group * rows_per_wave * (double)n_cols < 4294967296.0,
+// a swept block (companion.h) of which no workgroup sees 2^32 entries: its bins are 32-bit
+int plan_profile(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, Launch* l) {
+    const int rc = plan_launch(S, layout, stride, n_rows, n_cols, true, l);
+    if (rc) return rc;
+    REQUIRE((double)l->rows * (double)n_cols < 4294967296.0,
             "a block of %lld x %lld gives one workgroup 2^32 entries or more: sweep it in pieces of fewer rows",
             (long long)n_rows, (long long)n_cols);
-    out->vec = rowmajor && aligned && (stride % (layout == ROWMAJOR_F64 ? 2 : 4)) == 0;
     return SIMRANK_PROFILE_OK;
 }
 
@@ -309,7 +243,7 @@ int simrank_profile_version(void) { return SIMRANK_PROFILE_VERSION; }
 const char* simrank_profile_last_error(void) { return g_error.c_str(); }
 
 int simrank_profile_key_bits(int32_t layout) {
-    REQUIRE(layout >= PANEL_F32 && layout <= ROWMAJOR_F64, "unknown layout %d", (int)layout);
+    REQUIRE(known_layout(layout), "unknown layout %d", (int)layout);
     return layout == PANEL_F16 ? 16 : layout == ROWMAJOR_F64 ? 64 : 32;
 }
 
@@ -317,7 +251,7 @@ int simrank_profile_count(const void* S, int32_t layout, int64_t stride, int64_t
                           const int32_t* row_ids, const int32_t* col_ids, const void* edges, int32_t n_edges,
                           uint64_t* counts, void* stream) {
     Launch l;
-    const int rc = plan_launch(S, layout, stride, n_rows, n_cols, &l);
+    const int rc = plan_profile(S, layout, stride, n_rows, n_cols, &l);
     if (rc) return rc;
     REQUIRE(n_edges >= 1 && n_edges <= kMaxEdges, "n_edges must be 1 .. %d (got %d)", kMaxEdges, (int)n_edges);
     REQUIRE(edges && counts, "edges or counts is NULL");
@@ -327,20 +261,15 @@ int simrank_profile_count(const void* S, int32_t layout, int64_t stride, int64_t
     hipStream_t st = as_stream(stream);
     unsigned long long* out = reinterpret_cast<unsigned long long*>(counts);
     const bool agg = !plain_bins();
-#define COUNT_LAUNCH(LAYOUT, AGG)                                                                                       \
-    hipLaunchKernelGGL((count_kernel<LAYOUT, AGG>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols,     \
-                       row_ids, col_ids, static_cast<const Elem<LAYOUT>::Cmp*>(edges), (int)n_edges, top, out, l.vec)
-#define COUNT_BOTH(LAYOUT)             \
-    do {                               \
-        if (agg) COUNT_LAUNCH(LAYOUT, true); \
-        else COUNT_LAUNCH(LAYOUT, false);    \
-    } while (0)
-    if (layout == PANEL_F32) COUNT_BOTH(PANEL_F32);
-    else if (layout == ROWMAJOR_F32) COUNT_BOTH(ROWMAJOR_F32);
-    else if (layout == PANEL_F16) COUNT_BOTH(PANEL_F16);
-    else COUNT_BOTH(ROWMAJOR_F64);
-#undef COUNT_BOTH
-#undef COUNT_LAUNCH
+    with_layout(layout, [&](auto L) {
+        const auto* e = static_cast<const typename Elem<L>::Cmp*>(edges);
+        if (agg)
+            hipLaunchKernelGGL((count_kernel<L, true>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols,
+                               row_ids, col_ids, e, (int)n_edges, top, out, l.vec);
+        else
+            hipLaunchKernelGGL((count_kernel<L, false>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols,
+                               row_ids, col_ids, e, (int)n_edges, top, out, l.vec);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_PROFILE_OK;
 }
@@ -349,7 +278,7 @@ int simrank_profile_digits(const void* S, int32_t layout, int64_t stride, int64_
                            const int32_t* row_ids, const int32_t* col_ids, uint64_t prefix, int32_t prefix_bits,
                            int32_t digit_bits, uint64_t* hist, uint64_t* min_above, void* stream) {
     Launch l;
-    const int rc = plan_launch(S, layout, stride, n_rows, n_cols, &l);
+    const int rc = plan_profile(S, layout, stride, n_rows, n_cols, &l);
     if (rc) return rc;
     const int key_bits = layout == PANEL_F16 ? 16 : layout == ROWMAJOR_F64 ? 64 : 32;
     REQUIRE(digit_bits >= 1 && digit_bits <= SIMRANK_PROFILE_MAX_DIGIT_BITS, "digit_bits must be 1 .. %d (got %d)",
@@ -363,20 +292,14 @@ int simrank_profile_digits(const void* S, int32_t layout, int64_t stride, int64_
     unsigned long long* out = reinterpret_cast<unsigned long long*>(hist);
     unsigned long long* mn = reinterpret_cast<unsigned long long*>(min_above);
     const bool agg = !plain_bins();
-#define DIGITS_LAUNCH(LAYOUT, AGG)                                                                                      \
-    hipLaunchKernelGGL((digits_kernel<LAYOUT, AGG>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols,    \
-                       row_ids, col_ids, prefix, (int)prefix_bits, (int)digit_bits, out, mn, l.vec)
-#define DIGITS_BOTH(LAYOUT)             \
-    do {                                \
-        if (agg) DIGITS_LAUNCH(LAYOUT, true); \
-        else DIGITS_LAUNCH(LAYOUT, false);    \
-    } while (0)
-    if (layout == PANEL_F32) DIGITS_BOTH(PANEL_F32);
-    else if (layout == ROWMAJOR_F32) DIGITS_BOTH(ROWMAJOR_F32);
-    else if (layout == PANEL_F16) DIGITS_BOTH(PANEL_F16);
-    else DIGITS_BOTH(ROWMAJOR_F64);
-#undef DIGITS_BOTH
-#undef DIGITS_LAUNCH
+    with_layout(layout, [&](auto L) {
+        if (agg)
+            hipLaunchKernelGGL((digits_kernel<L, true>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols,
+                               row_ids, col_ids, prefix, (int)prefix_bits, (int)digit_bits, out, mn, l.vec);
+        else
+            hipLaunchKernelGGL((digits_kernel<L, false>), dim3(l.grid), dim3(kThreads), 0, st, S, stride, n_rows, n_cols,
+                               row_ids, col_ids, prefix, (int)prefix_bits, (int)digit_bits, out, mn, l.vec);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_PROFILE_OK;
 }

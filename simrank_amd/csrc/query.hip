@@ -133,33 +133,6 @@ __global__ __launch_bounds__(256) void query_topk_kernel(const void* __restrict_
     }
 }
 
-int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols) {
-    REQUIRE(layout >= SIMRANK_QUERY_PANEL_F32 && layout <= SIMRANK_QUERY_ROWMAJOR_F64, "unknown layout %d", (int)layout);
-    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
-                "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    REQUIRE(S || n_rows == 0 || n_cols == 0, "S is NULL");
-    const bool panels = layout == SIMRANK_QUERY_PANEL_F32 || layout == SIMRANK_QUERY_PANEL_F16;
-    REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
-                panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
-    return SIMRANK_QUERY_OK;
-}
-
-#define QRY_DISPATCH(layout, KERNEL, grid, block, stream, ...)                                                             \
-    switch (layout) {                                                                                                      \
-        case SIMRANK_QUERY_PANEL_F32:                                                                                      \
-            hipLaunchKernelGGL(KERNEL<SIMRANK_QUERY_PANEL_F32>, grid, block, 0, stream, __VA_ARGS__);                      \
-            break;                                                                                                         \
-        case SIMRANK_QUERY_ROWMAJOR_F32:                                                                                   \
-            hipLaunchKernelGGL(KERNEL<SIMRANK_QUERY_ROWMAJOR_F32>, grid, block, 0, stream, __VA_ARGS__);                   \
-            break;                                                                                                         \
-        case SIMRANK_QUERY_PANEL_F16:                                                                                      \
-            hipLaunchKernelGGL(KERNEL<SIMRANK_QUERY_PANEL_F16>, grid, block, 0, stream, __VA_ARGS__);                      \
-            break;                                                                                                         \
-        default:                                                                                                           \
-            hipLaunchKernelGGL(KERNEL<SIMRANK_QUERY_ROWMAJOR_F64>, grid, block, 0, stream, __VA_ARGS__);                   \
-            break;                                                                                                         \
-    }
-
 }  // namespace
 
 extern "C" {
@@ -183,8 +156,10 @@ int simrank_query_rows(const void* S, int32_t layout, int64_t stride, int64_t n_
     REQUIRE(blocks < (int64_t(1) << 31), "%lld x %lld values are too many for one call: cut the query rows into bands",
                 (long long)n_q, (long long)n_out);
     hipStream_t st = as_stream(stream);
-    QRY_DISPATCH(layout, query_rows_kernel, dim3((unsigned)blocks), dim3(kRowsThreads), st, S, stride, n_rows, n_cols, row_pos,
-                 n_q, col_pos, n_out, chunks, out, ld_out);
+    with_layout(layout, [&](auto L) {
+        hipLaunchKernelGGL(query_rows_kernel<L>, dim3((unsigned)blocks), dim3(kRowsThreads), 0, st, S, stride, n_rows,
+                           n_cols, row_pos, n_q, col_pos, n_out, chunks, out, ld_out);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_QUERY_OK;
 }
@@ -198,7 +173,10 @@ int simrank_query_pairs(const void* S, int32_t layout, int64_t stride, int64_t n
     REQUIRE(a_pos && b_pos && out, "a_pos, b_pos or out is NULL");
     hipStream_t st = as_stream(stream);
     const unsigned grid = (unsigned)((n_pairs + 255) / 256);
-    QRY_DISPATCH(layout, query_pairs_kernel, dim3(grid), dim3(256), st, S, stride, n_rows, n_cols, a_pos, b_pos, n_pairs, out);
+    with_layout(layout, [&](auto L) {
+        hipLaunchKernelGGL(query_pairs_kernel<L>, dim3(grid), dim3(256), 0, st, S, stride, n_rows, n_cols, a_pos, b_pos,
+                           n_pairs, out);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_QUERY_OK;
 }
@@ -214,8 +192,10 @@ int simrank_query_topk(const void* S, int32_t layout, int64_t stride, int64_t n_
     REQUIRE(row_pos && row_ids && idx_out && val_out, "row_pos, row_ids, idx_out or val_out is NULL");
     hipStream_t st = as_stream(stream);
     const unsigned grid = (unsigned)std::min<int64_t>((n_q + 3) / 4, int64_t(1) << 16);
-    QRY_DISPATCH(layout, query_topk_kernel, dim3(grid), dim3(256), st, S, stride, n_rows, n_cols, row_pos, row_ids, n_q, col_ids,
-                 (int)k, idx_out, val_out);
+    with_layout(layout, [&](auto L) {
+        hipLaunchKernelGGL(query_topk_kernel<L>, dim3(grid), dim3(256), 0, st, S, stride, n_rows, n_cols, row_pos, row_ids,
+                           n_q, col_ids, (int)k, idx_out, val_out);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_QUERY_OK;
 }

@@ -32,32 +32,20 @@ COMPANION_SAME_LAYOUT(SIMRANK_SELECT_, PANEL_F32);
 COMPANION_SAME_LAYOUT(SIMRANK_SELECT_, ROWMAJOR_F32);
 COMPANION_SAME_LAYOUT(SIMRANK_SELECT_, PANEL_F16);
 
-typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
-
-// One kernel for both passes and the three layouts.  Panel layouts: a wave takes EIGHT consecutive rows, lane group
-// g = lane >> 3 owns row 8 w + g, lane q = lane & 7 the 16 bytes at 16 q of every panel's row segment (4 f32 or 8 fp16
-// values) — one load instruction reads the eight rows' segments of a panel, 1 KiB contiguous (the pattern of
-// topk_rows_blocked_onepass_kernel).  Row-major: a wave takes one row, 4 columns per lane, 256 per load instruction.
-// Four loads in flight per lane.  A lane's columns precede those of the next lane of its row, so a hit's rank in its
-// row is (hits of the row's lower lanes) + (the lane's own earlier hits): ballots and popcounts.
+// One kernel for both passes and the three layouts, on the shared walk (companion.h: eight rows per wave on panels, one
+// on a row-major block, four 16-byte loads in flight per lane).  A lane's columns precede those of the next lane of its
+// row, so a hit's rank in its row is (hits of the row's lower lanes) + (the lane's own earlier hits): ballots and
+// popcounts.
 template <int LAYOUT, bool EMIT>
-__global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ S, int64_t stride, int64_t n_rows,
-                                                     int64_t n_cols, const int32_t* __restrict__ row_ids,
-                                                     const int32_t* __restrict__ col_ids, float t32,
-                                                     int32_t* __restrict__ counts, const int64_t* __restrict__ offsets,
-                                                     int64_t capacity, int32_t* __restrict__ ids_out,
-                                                     float* __restrict__ vals_out, int vec) {
-    constexpr bool ROWMAJOR = LAYOUT == SIMRANK_SELECT_ROWMAJOR_F32;
-    constexpr bool HALF = LAYOUT == SIMRANK_SELECT_PANEL_F16;
-    constexpr int V = HALF ? 8 : 4;              // values per lane and 16-byte load
-    constexpr int L = ROWMAJOR ? 64 : 8;         // lanes per row
-    constexpr int R = 64 / L;                    // rows per wave
-    constexpr int W = L * V;                     // columns per chunk: a panel, or 256 columns of a row
-    constexpr int U = 4;                         // chunks in flight
-    const int lane = threadIdx.x & 63, g = lane / L, q = lane % L;
-    const int64_t wave = (blockIdx.x * int64_t(blockDim.x) + threadIdx.x) >> 6;
-    const int64_t nwaves = (int64_t(gridDim.x) * blockDim.x) >> 6;
-    const int64_t n_chunks = (n_cols + W - 1) / W;
+__global__ __launch_bounds__(kSweepThreads) void select_kernel(const void* __restrict__ S, int64_t stride, int64_t n_rows,
+                                                               int64_t n_cols, const int32_t* __restrict__ row_ids,
+                                                               const int32_t* __restrict__ col_ids, float t32,
+                                                               int32_t* __restrict__ counts,
+                                                               const int64_t* __restrict__ offsets, int64_t capacity,
+                                                               int32_t* __restrict__ ids_out, float* __restrict__ vals_out,
+                                                               int vec) {
+    using E = Elem<LAYOUT>;
+    WALK_GEOMETRY(LAYOUT, n_cols);
     const uint64_t row_mask = L == 64 ? ~0ull : (0xffull << (8 * g));
     const uint64_t lower = row_mask & ((1ull << lane) - 1);          // the row's lanes before this one
     for (int64_t r0 = wave * R; r0 < n_rows; r0 += nwaves * R) {
@@ -71,39 +59,13 @@ __global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ S,
         }
         int32_t cnt = 0;
         for (int64_t k0 = 0; k0 < n_chunks; k0 += U) {
-            v4u32 x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int64_t k = k0 + u;
-                x[u] = v4u32{0, 0, 0, 0};
-                if (!live || k >= n_chunks) continue;
-                if (!ROWMAJOR) {
-                    x[u] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(S) + ((k * stride + r) * 8 + q));
-                } else {
-                    const float* row = reinterpret_cast<const float*>(S) + r * stride;
-                    const int64_t c0 = k * W + 4 * q;
-                    if (vec && c0 + 3 < n_cols) {
-                        x[u] = __builtin_nontemporal_load(reinterpret_cast<const v4u32*>(row + c0));
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-                            if (c0 + i < n_cols) x[u][i] = __float_as_uint(row[c0 + i]);
-                    }
-                }
-            }
+            WALK_LOAD(LAYOUT, x, S, stride, r, live, k0, n_cols, vec)
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int64_t c0 = (k0 + u) * W + int64_t(q) * V;
                 float v[V];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    if (HALF) {       // fp16 -> f32 is exact, x 2^-14 is exact: the bits the dense hand-back widens
-                        v[2 * j] = float(__builtin_bit_cast(_Float16, (unsigned short)(x[u][j] & 0xffffu))) * 0x1p-14f;
-                        v[2 * j + 1] = float(__builtin_bit_cast(_Float16, (unsigned short)(x[u][j] >> 16))) * 0x1p-14f;
-                    } else {
-                        v[j] = __uint_as_float(x[u][j]);
-                    }
-                }
+                for (int i = 0; i < V; ++i) v[i] = E::value(E::raw(x[u], i));
                 unsigned hit = 0;
                 int32_t cid[V];
 #pragma unroll
@@ -149,36 +111,25 @@ __global__ __launch_bounds__(256) void select_kernel(const void* __restrict__ S,
     }
 }
 
-int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, float t32) {
-    REQUIRE(layout == SIMRANK_SELECT_PANEL_F32 || layout == SIMRANK_SELECT_ROWMAJOR_F32 ||
-                    layout == SIMRANK_SELECT_PANEL_F16, "unknown layout %d", (int)layout);
-    REQUIRE(n_rows > 0 && n_cols >= 0 && n_cols < (int64_t(1) << 31) && n_rows < (int64_t(1) << 31),
-                "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    REQUIRE(n_cols == 0 || S, "S is NULL");
-    REQUIRE(layout == SIMRANK_SELECT_ROWMAJOR_F32 ? stride >= n_cols : stride >= n_rows,
-                "stride %lld is too small for %lld x %lld", (long long)stride, (long long)n_rows, (long long)n_cols);
-    REQUIRE(layout == SIMRANK_SELECT_ROWMAJOR_F32 || (reinterpret_cast<uintptr_t>(S) & 15) == 0,
-                "a panel-blocked block must be 16-byte aligned");
+// a swept block (companion.h) with select's own rules on top: at least one row, no float64 iterate, a threshold > 0
+int plan_select(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, float t32, Launch* l) {
+    REQUIRE(known_layout(layout) && layout != ROWMAJOR_F64, "unknown layout %d", (int)layout);
+    REQUIRE(n_rows > 0, "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
+    const int rc = plan_launch(S, layout, stride, n_rows, n_cols, false, l);
+    if (rc) return rc;
     REQUIRE(t32 > 0.f, "the threshold must be > 0");
     return SIMRANK_SELECT_OK;
 }
 
 template <bool EMIT>
-int launch(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols, const int32_t* row_ids,
-           const int32_t* col_ids, float t32, int32_t* counts, const int64_t* offsets, int64_t capacity, int32_t* ids_out,
-           float* vals_out, void* stream) {
-    const int64_t rows_per_wave = layout == SIMRANK_SELECT_ROWMAJOR_F32 ? 1 : 8;
-    const int64_t waves = (n_rows + rows_per_wave - 1) / rows_per_wave;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, 256 * 8));
-    const int vec = layout == SIMRANK_SELECT_ROWMAJOR_F32 && (stride & 3) == 0 && (reinterpret_cast<uintptr_t>(S) & 15) == 0;
-    hipStream_t st = as_stream(stream);
-#define SEL_LAUNCH(LAYOUT)                                                                                            \
-    hipLaunchKernelGGL((select_kernel<LAYOUT, EMIT>), dim3(grid), dim3(256), 0, st, S, stride, n_rows, n_cols, row_ids, \
-                       col_ids, t32, counts, offsets, capacity, ids_out, vals_out, vec)
-    if (layout == SIMRANK_SELECT_PANEL_F32) SEL_LAUNCH(SIMRANK_SELECT_PANEL_F32);
-    else if (layout == SIMRANK_SELECT_ROWMAJOR_F32) SEL_LAUNCH(SIMRANK_SELECT_ROWMAJOR_F32);
-    else SEL_LAUNCH(SIMRANK_SELECT_PANEL_F16);
-#undef SEL_LAUNCH
+int launch(const Launch& l, const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols,
+           const int32_t* row_ids, const int32_t* col_ids, float t32, int32_t* counts, const int64_t* offsets,
+           int64_t capacity, int32_t* ids_out, float* vals_out, void* stream) {
+    with_layout(layout, [&](auto L) {
+        if constexpr (L != ROWMAJOR_F64)
+            hipLaunchKernelGGL((select_kernel<L, EMIT>), dim3(l.grid), dim3(kSweepThreads), 0, as_stream(stream), S, stride,
+                               n_rows, n_cols, row_ids, col_ids, t32, counts, offsets, capacity, ids_out, vals_out, l.vec);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_SELECT_OK;
 }
@@ -219,14 +170,15 @@ int simrank_select_threshold_f32(double t, float* t32) {
 
 int simrank_select_count(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols,
                          const int32_t* row_ids, const int32_t* col_ids, float t32, int32_t* counts, void* stream) {
-    const int rc = check_block(S, layout, stride, n_rows, n_cols, t32);
+    Launch l;
+    const int rc = plan_select(S, layout, stride, n_rows, n_cols, t32, &l);
     if (rc) return rc;
     REQUIRE(counts, "counts is NULL");
     if (n_cols == 0) {
         HIP_CHECK(hipMemsetAsync(counts, 0, size_t(n_rows) * sizeof(int32_t), as_stream(stream)));
         return SIMRANK_SELECT_OK;
     }
-    return launch<false>(S, layout, stride, n_rows, n_cols, row_ids, col_ids, t32, counts, nullptr, 0, nullptr, nullptr,
+    return launch<false>(l, S, layout, stride, n_rows, n_cols, row_ids, col_ids, t32, counts, nullptr, 0, nullptr, nullptr,
                          stream);
 }
 
@@ -246,11 +198,12 @@ int simrank_select_offsets(const int32_t* counts, int64_t n_rows, int64_t* offse
 int simrank_select_emit(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols,
                         const int32_t* row_ids, const int32_t* col_ids, float t32, const int64_t* offsets, int64_t capacity,
                         int32_t* ids_out, float* vals_out, void* stream) {
-    const int rc = check_block(S, layout, stride, n_rows, n_cols, t32);
+    Launch l;
+    const int rc = plan_select(S, layout, stride, n_rows, n_cols, t32, &l);
     if (rc) return rc;
     REQUIRE(offsets && capacity >= 0 && (capacity == 0 || (ids_out && vals_out)), "bad emit arguments");
     if (n_cols == 0 || capacity == 0) return SIMRANK_SELECT_OK;
-    return launch<true>(S, layout, stride, n_rows, n_cols, row_ids, col_ids, t32, nullptr, offsets, capacity, ids_out,
+    return launch<true>(l, S, layout, stride, n_rows, n_cols, row_ids, col_ids, t32, nullptr, offsets, capacity, ids_out,
                         vals_out, stream);
 }
 

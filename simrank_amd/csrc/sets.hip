@@ -248,25 +248,14 @@ int64_t grid_blocks(int64_t n_sets, int64_t n_out, int32_t grid_order) {
     return 8 * ((n_sets + fewest - 1) / fewest);
 }
 
-int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_rows, int64_t n_cols) {
-    REQUIRE(layout >= SIMRANK_SETS_PANEL_F32 && layout <= SIMRANK_SETS_ROWMAJOR_F64, "unknown layout %d", (int)layout);
-    REQUIRE(n_rows >= 0 && n_cols >= 0 && n_rows < (int64_t(1) << 31) && n_cols < (int64_t(1) << 31),
-            "bad block shape %lld x %lld", (long long)n_rows, (long long)n_cols);
-    REQUIRE(S || n_rows == 0 || n_cols == 0, "S is NULL");
-    const bool panels = layout == SIMRANK_SETS_PANEL_F32 || layout == SIMRANK_SETS_PANEL_F16;
-    REQUIRE(stride >= (panels ? n_rows : n_cols), "stride %lld is smaller than the block's %s (%lld)", (long long)stride,
-            panels ? "rows" : "columns", (long long)(panels ? n_rows : n_cols));
-    return SIMRANK_SETS_OK;
-}
-
 // Whether every quad of 4 columns that lies inside the block is one aligned vector load: panels always are (32 and 64
 // divide by 4, a panel row is 128 bytes); a row-major block when its rows start on 16 (f32) or 16 (float64) bytes.
 bool vector_loads(const void* S, int32_t layout, int64_t stride) {
     const uintptr_t p = reinterpret_cast<uintptr_t>(S);
     switch (layout) {
-        case SIMRANK_SETS_PANEL_F32: return p % 16 == 0;
-        case SIMRANK_SETS_PANEL_F16: return p % 8 == 0;
-        case SIMRANK_SETS_ROWMAJOR_F32: return p % 16 == 0 && stride % 4 == 0;
+        case PANEL_F32: return p % 16 == 0;
+        case PANEL_F16: return p % 8 == 0;
+        case ROWMAJOR_F32: return p % 16 == 0 && stride % 4 == 0;
         default: return p % 16 == 0 && stride % 2 == 0;
     }
 }
@@ -318,16 +307,10 @@ int simrank_sets_score(const void* S, int32_t layout, int64_t stride, int64_t n_
     const bool vec = !col_pos && vector_loads(S, layout, stride);
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)blocks);
-#define SETS_SCORE(L)                                                                                                     \
-    launch_score<L>(vec, grid, st, S, stride, n_rows, n_cols, col_pos, n_out, set_ptr, set_pos, set_w, n_sets, excl_ptr,  \
-                    excl_cols, chunks, (int)grid_order, out, ld_out)
-    switch (layout) {
-        case SIMRANK_SETS_PANEL_F32: SETS_SCORE(PANEL_F32); break;
-        case SIMRANK_SETS_ROWMAJOR_F32: SETS_SCORE(ROWMAJOR_F32); break;
-        case SIMRANK_SETS_PANEL_F16: SETS_SCORE(PANEL_F16); break;
-        default: SETS_SCORE(ROWMAJOR_F64); break;
-    }
-#undef SETS_SCORE
+    with_layout(layout, [&](auto L) {
+        launch_score<L>(vec, grid, st, S, stride, n_rows, n_cols, col_pos, n_out, set_ptr, set_pos, set_w, n_sets, excl_ptr,
+                        excl_cols, chunks, (int)grid_order, out, ld_out);
+    });
     HIP_CHECK(hipGetLastError());
     return SIMRANK_SETS_OK;
 }

@@ -68,7 +68,8 @@ def dev(device):
     device.release()
 
 
-SHAPES = [(1, 1), (7, 33), (8, 64), (9, 65), (33, 31), (129, 257), (64, 700)]
+# (3, 1029): a row-major f32 row past one group of four chunks in flight (1024 columns), with a ragged tail
+SHAPES = [(1, 1), (7, 33), (8, 64), (9, 65), (33, 31), (129, 257), (64, 700), (3, 1029)]
 
 
 def id_cases(n_rows, n_cols, rng):

@@ -29,17 +29,21 @@ def test_companion_links_nothing_of_the_main_library():
 
 
 def test_layout_codes_agree_across_headers_and_bindings():
-    """One set of layout codes: ``engine._iterate_block`` hands a plan's "iterate_layout" to the select, query and
-    fold-in libraries alike, and ``_foldin.Folder`` passes a query code to fold-in calls (csrc/companion.h asserts the
-    same of the three headers when the libraries are compiled)."""
-    from simrank_amd import _companion, _foldin, _select
+    """One set of layout codes: ``engine._iterate_block`` hands a plan's "iterate_layout" to every library that reads a
+    block alike, and ``_foldin.Folder`` passes a query code to fold-in calls (csrc/companion.h asserts the same of the
+    headers when the libraries are compiled)."""
+    from simrank_amd import _cluster, _companion, _foldin, _model, _neighbors, _profile, _select, _sets
     want = {"PANEL_F32": 0, "ROWMAJOR_F32": 1, "PANEL_F16": 2, "ROWMAJOR_F64": 3}
-    assert A.layout_codes(_query) == want and A.layout_codes(_foldin) == want
+    # _query, _model, _profile and _cluster define all four names.  _sets and _neighbors define no layout name at all:
+    # their callers pass them a block's code, so only their headers can be checked.
+    named = (_query, _model, _profile, _cluster)
+    for mod in named + (_foldin, _sets, _neighbors):
+        assert A.layout_codes(mod) == want, mod.__name__
     three = {k: v for k, v in want.items() if k != "ROWMAJOR_F64"}            # (select reads no float64 iterate)
     assert A.layout_codes(_select) == three
-    for mod, names in ((_companion, want), (_query, want), (_select, three), (_foldin, ["ROWMAJOR_F64"])):
+    for mod, names in [(_companion, want), (_select, three), (_foldin, ["ROWMAJOR_F64"])] + [(m, want) for m in named]:
         for name in names:
-            assert getattr(mod, name) == want[name], (mod.__name__, name)
+            assert getattr(mod, name) == getattr(_companion, name) == want[name], (mod.__name__, name)
 
 
 def test_main_library_abi_is_unchanged():
