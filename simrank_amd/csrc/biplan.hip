@@ -9,7 +9,8 @@
 // One edge set describes both patterns: W12 = diag(rowscale1) . A (n1 x n2), W21 = diag(rowscale2) . A^T.
 // Each update is two launches (leg 1: fused_trans_kernel on a rectangular pattern, leg 2: upper-triangle gather
 // with the fused epilogue and count); iteration k + 1 is queued before the counts of iteration k are read, as in
-// plan.hip.  Evidence: by default the corrected form — E1 from the group-1 pattern, E2 from the group-2 pattern.
+// plan.hip (the loop itself is loop.h's; a matrix and the functions over it are side.h's, group w's operand being the
+// other group's side).  Evidence: by default the corrected form — E1 from the group-1 pattern, E2 from the group-2 pattern.
 // options.strict_reference = 1 is the reference's own behaviour (SimRank.py:420-423, :488-491, SURVEY.md quirk
 // Q2): BOTH updates are multiplied by Evidence_N1, position by position in the caller's node order — n1 = n2:
 // the group-2 update is gated by the counts of the group-1 pattern; n1 = 1: NumPy broadcasts the 1 x 1 array,
@@ -24,26 +25,10 @@
 #include <string>
 #include <thread>
 
-#include "common.h"
+#include "loop.h"
+#include "side.h"
 
-namespace {
-
-struct side_t {
-    int64_t n = 0, k = 0, rows_pad = 0, k_rows_pad = 0;    // n: own group, k: the other group
-    size_t mat_bytes = 0, t_bytes = 0;
-    simrank_graph* g = nullptr;                // n x k, solver order on both sides
-    float* S[2] = {nullptr, nullptr};          // n x n, panel-blocked, ping-pong
-    float* Tt = nullptr;                       // k x n: (W . S_other)^T
-    uint8_t* ev = nullptr;
-    float* prior = nullptr;
-    int32_t* inv = nullptr;                    // device: position of caller's node i in the solver's order
-    int32_t* ord_dev = nullptr;                // device: caller's node at position r (simrank_biplan_get "ids")
-    float coef = 0.8f, lbd = 0.f;
-    int32_t restrict_support = 0;
-    int cur = 0;
-};
-
-}  // namespace
+using simrank::side_t;
 
 struct simrank_biplan {
     side_t s[2];
@@ -62,43 +47,13 @@ namespace simrank {
 
 static int side_update(simrank_biplan* p, int w, double eps, int32_t exact_count, unsigned long long* host_slot) {
     side_t& a = p->s[w];
-    const side_t& o = p->s[w ^ 1];
-    // leg 1: Tt (k x n) = (W . S_other)^T; S_other is k x k — the identity for the very first update of group 1 (SimRank.py:280-285:
-    // group 2's first update already reads the new S1), whose product is W^T written directly: the same bits, no gathers
+    // S_other is the identity for the very first update of group 1 (SimRank.py:280-285: group 2's first update already reads
+    // the new S1)
     const bool from_identity = w == 0 && p->at_identity && p->identity_leg1;
     if (w == 0) p->at_identity = 0;
-    int rc = from_identity ? identity_leg1_blocked(a.g, a.Tt, a.k_rows_pad, p->stream)
-                           : simrank_spmm_blocked(a.g, o.S[o.cur], o.rows_pad, a.k, a.Tt, a.k_rows_pad, 1, nullptr, p->stream);
+    const int rc = side_leg_pair(a, p->s[w ^ 1], from_identity, p->asym != 0, eps, exact_count, p->counters, host_slot, p->stream,
+                                 [] { return SIMRANK_OK; });
     if (rc) return rc;
-    simrank_epilogue ep{};
-    ep.coef = a.coef;
-    ep.lbd = a.lbd;
-    ep.evidence = a.ev;
-    ep.ld_evidence = 32;
-    ep.apriori = a.prior;
-    ep.ld_apriori = 32;
-    ep.previous = a.S[a.cur];
-    ep.ld_previous = 32;
-    ep.eps = eps;
-    ep.n_changed = p->counters;
-    ep.diag_col0 = 0;
-    ep.set_diag = 1;
-    ep.symmetric = 1;
-    ep.restrict_support = a.restrict_support;
-    ep.count_any = exact_count ? 0 : 1;
-    if (p->asym) {
-        // asymmetric iterates (SimRank.py:488, :491 with a prior that is not symmetric): W . Tt is the transpose of
-        // W S_other W^T — stored transposed, then the epilogue as a pass of its own (exact count)
-        ep.symmetric = 0;
-        ep.restrict_support = 0;
-        rc = simrank_spmm_blocked(a.g, a.Tt, a.k_rows_pad, a.n, a.S[a.cur ^ 1], a.rows_pad, 1, nullptr, p->stream);
-        if (!rc) rc = simrank_epilogue_apply_blocked(a.S[a.cur ^ 1], a.S[a.cur ^ 1], a.n, a.n, a.rows_pad, &ep, p->stream);
-    } else {
-        rc = simrank_spmm_blocked(a.g, a.Tt, a.k_rows_pad, a.n, a.S[a.cur ^ 1], a.rows_pad, 0, &ep, p->stream);
-    }
-    if (rc) return rc;
-    SR_HIP(hipMemcpyAsync(host_slot, p->counters, sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS,
-                          hipMemcpyDeviceToHost, p->stream));
     a.cur ^= 1;              // (the group-2 update of the same iteration reads the new S1)
     return SIMRANK_OK;
 }
@@ -134,11 +89,7 @@ extern "C" {
 int simrank_biplan_destroy(simrank_biplan* p) {
     if (!p) return SIMRANK_OK;
     if (p->stream) (void)hipStreamSynchronize(p->stream);
-    for (side_t& a : p->s) {
-        (void)pool_free(a.S[0]); (void)pool_free(a.S[1]); (void)pool_free(a.Tt); (void)pool_free(a.ev);
-        (void)pool_free(a.prior); (void)pool_free(a.inv); (void)pool_free(a.ord_dev);
-        simrank_graph_destroy(a.g);
-    }
+    for (side_t& a : p->s) side_free(a);
     (void)pool_free(p->counters);
     for (int i = 0; i < 2; ++i) {
         for (int w = 0; w < 2; ++w)
@@ -155,8 +106,7 @@ int simrank_biplan_reset(simrank_biplan* p) {
     p->updates = 0;
     p->at_identity = 1;
     for (side_t& a : p->s) {
-        a.cur = 0;
-        const int rc = simrank_fill_identity_blocked(a.S[0], a.n, a.n, a.rows_pad, 0, p->stream);
+        const int rc = side_reset(a, p->stream);
         if (rc) return rc;
     }
     return SIMRANK_OK;
@@ -201,14 +151,9 @@ int simrank_biplan_create(int64_t n1, int64_t n2, int64_t nnz, const int32_t* ro
         std::string errs[2];
         for (int w = 0; w < 2; ++w) {
             side_t& a = p->s[w];
-            a.n = ns[w];
-            a.k = ns[w ^ 1];
+            side_shape(a, ns[w], ns[w ^ 1], false);
             a.coef = w == 0 ? opt->c1 : opt->c2;
             a.lbd = w == 0 ? opt->lbd1 : opt->lbd2;
-            a.rows_pad = (a.n + 7) / 8 * 8 + 8;
-            a.k_rows_pad = (a.k + 7) / 8 * 8 + 8;
-            a.mat_bytes = size_t((a.n + 31) / 32) * size_t(a.rows_pad) * 32 * sizeof(float);     // n x n
-            a.t_bytes = size_t((a.n + 31) / 32) * size_t(a.k_rows_pad) * 32 * sizeof(float);      // k x n
             if (tw[w].fuse == 1 && ((tw[w].triangle && a.n >= 64) || p->asym) && a.k <= tw[w].fuse_max_rows &&
                 (a.k_rows_pad + 1) * 128 < (int64_t(1) << 31))
                 tw[w].dense_lazy = 1;
@@ -237,45 +182,32 @@ int simrank_biplan_create(int64_t n1, int64_t n2, int64_t nnz, const int32_t* ro
                 return fail(rcs[w]);
             }
     }
-#define BIPLAN_HIP(call)                                                                          \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            (void)hipGetLastError();                                                              \
-            return fail(e_ == hipErrorOutOfMemory ? SIMRANK_ERR_ALLOC : SIMRANK_ERR_HIP);         \
-        }                                                                                         \
-    } while (0)
     lap("graph objects");
-    BIPLAN_HIP(pool_hip_alloc((void**)&p->counters, sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS));
-    for (int i = 0; i < 2; ++i) {
-        for (int w = 0; w < 2; ++w)
-            BIPLAN_HIP(hipHostMalloc((void**)&p->host_counters[i][w], sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS,
-                                     hipHostMallocPortable));
-        BIPLAN_HIP(hipEventCreateWithFlags(&p->counted[i], hipEventDisableTiming));
-    }
+    auto counters = [&]() -> int {
+        SIDE_HIP(pool_hip_alloc((void**)&p->counters, sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS));
+        for (int i = 0; i < 2; ++i) {
+            for (int w = 0; w < 2; ++w)
+                SIDE_HIP(hipHostMalloc((void**)&p->host_counters[i][w], sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS,
+                                       hipHostMallocPortable));
+            SIDE_HIP(hipEventCreateWithFlags(&p->counted[i], hipEventDisableTiming));
+        }
+        return SIMRANK_OK;
+    };
+    int rc = counters();
+    if (rc) return fail(rc);
     for (int w = 0; w < 2; ++w) {
         side_t& a = p->s[w];
-        // (no memset: as in plan.hip — reset fills S[0], every update writes all of Tt and of the other iterate first)
-        for (float** b : {&a.S[0], &a.S[1]}) BIPLAN_HIP(pool_hip_alloc((void**)b, a.mat_bytes));
-        BIPLAN_HIP(pool_hip_alloc((void**)&a.Tt, a.t_bytes));
-        BIPLAN_HIP(pool_hip_alloc((void**)&a.inv, size_t(a.n) * sizeof(int32_t)));
-        BIPLAN_HIP(hipMemcpyAsync(a.inv, inv[w].data(), size_t(a.n) * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
-        BIPLAN_HIP(pool_hip_alloc((void**)&a.ord_dev, size_t(a.n) * sizeof(int32_t)));
-        BIPLAN_HIP(hipMemcpyAsync(a.ord_dev, ord[w].data(), size_t(a.n) * sizeof(int32_t), hipMemcpyHostToDevice, p->stream));
-        BIPLAN_HIP(hipStreamSynchronize(p->stream));
+        rc = side_alloc(a, ord[w], inv[w], p->stream);
+        if (rc) return fail(rc);
         const bool q2 = opt->evidence && opt->strict_reference && w == 1;      // Evidence_N1 on the group-2 update
         if (q2 && n1 != n2 && n1 != 1) {
             p->broadcast_error = 1;
         } else if (opt->evidence) {
             // common-neighbour counts inside the group (SimRank.py:311-320 on this group's pattern)
-            const size_t ev_bytes = size_t((a.n + 31) / 32) * size_t(a.rows_pad) * 32;
-            BIPLAN_HIP(pool_hip_alloc((void**)&a.ev, ev_bytes));
-            int rc = SIMRANK_OK;
             if (q2 && n1 == 1 && n2 != 1) {
                 // the 1 x 1 Evidence_N1 broadcasts: the one group-1 node's count (with itself) gates every element
                 const int cnt = rowscale1[0] != 0.f ? (int)std::min<int64_t>(255, nnz) : 0;
-                BIPLAN_HIP(hipMemsetAsync(a.ev, cnt, ev_bytes, p->stream));
+                rc = side_evidence_alloc(a, cnt, p->stream);
             } else if (q2) {
                 // n1 = n2: element (i, j) of the group-2 update is multiplied by Evidence_N1[i][j], positions in the
                 // caller's order: the counts of the group-1 pattern with its rows taken in THIS group's solver order
@@ -292,47 +224,24 @@ int simrank_biplan_create(int64_t n1, int64_t n2, int64_t nnz, const int32_t* ro
                 simrank_graph* g1 = nullptr;
                 rc = simrank_graph_create(n1, n2, nnz, rp.data(), cl.data(), rs.data(), &g1);
                 if (rc) return fail(rc);
-                hipError_t e = hipMemsetAsync(a.ev, 0, ev_bytes, p->stream);
-                rc = e == hipSuccess ? simrank_evidence_counts_blocked(g1, 0, a.n, a.ev, a.rows_pad, p->stream) : SIMRANK_ERR_HIP;
+                rc = side_evidence_alloc(a, 0, p->stream);
+                if (!rc) rc = simrank_evidence_counts_blocked(g1, 0, a.n, a.ev, a.rows_pad, p->stream);
                 (void)hipStreamSynchronize(p->stream);
                 simrank_graph_destroy(g1);
             } else {
-                BIPLAN_HIP(hipMemsetAsync(a.ev, 0, ev_bytes, p->stream));
-                rc = simrank_evidence_counts_blocked(a.g, 0, a.n, a.ev, a.rows_pad, p->stream);
+                rc = side_evidence_alloc(a, 0, p->stream);
+                if (!rc) rc = simrank_evidence_counts_blocked(a.g, 0, a.n, a.ev, a.rows_pad, p->stream);
             }
+            if (!rc) rc = side_restrict(a, p->stream);
             if (rc) return fail(rc);
-            int64_t live = 0, total = 1;
-            rc = simrank_evidence_live_segments(a.ev, 32, a.rows_pad, a.n, a.n, &live, &total, p->stream);
-            if (rc) return fail(rc);
-            a.restrict_support = restrict_choice(a.g->tun, live, total);
         }
         if (priors[w]) {
-            float* tmp = nullptr;
-            int32_t* ord_dev = nullptr;
-            BIPLAN_HIP(pool_hip_alloc((void**)&tmp, size_t(a.n) * size_t(a.n) * sizeof(float)));
-            hipError_t e = pool_hip_alloc((void**)&ord_dev, size_t(a.n) * sizeof(int32_t));
-            if (e == hipSuccess) e = pool_hip_alloc((void**)&a.prior, a.mat_bytes);
-            if (e == hipSuccess) e = hipMemsetAsync(a.prior, 0, a.mat_bytes, p->stream);
-            if (e == hipSuccess) e = hipMemcpy2DAsync(tmp, size_t(a.n) * 4, priors[w], size_t(lds[w]) * 4, size_t(a.n) * 4,
-                                                      size_t(a.n), hipMemcpyHostToDevice, p->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(ord_dev, ord[w].data(), size_t(a.n) * 4, hipMemcpyHostToDevice, p->stream);
-            int rc = SIMRANK_OK;
-            if (e == hipSuccess) {
-                rc = simrank_permute_layout(tmp, a.n, 0, a.prior, 32, a.rows_pad, a.n, a.n, ord_dev, ord_dev, 4, p->stream);
-                e = hipStreamSynchronize(p->stream);
-            }
-            (void)pool_free(tmp);
-            (void)pool_free(ord_dev);
-            if (e != hipSuccess) {
-                set_error("plan prior upload: %s", hipGetErrorString(e));
-                return fail(SIMRANK_ERR_HIP);
-            }
+            rc = side_prior(a, priors[w], lds[w], p->stream);
             if (rc) return fail(rc);
         }
     }
-#undef BIPLAN_HIP
     lap("matrices, evidence counts, live segments, priors");
-    const int rc = simrank_biplan_reset(p);
+    rc = simrank_biplan_reset(p);
     if (rc) return fail(rc);
     lap("reset queued");
     *out = p;
@@ -360,54 +269,36 @@ int simrank_biplan_run_cb(simrank_biplan* p, int32_t iterations, double eps, sim
     SR_REQUIRE(p, "plan is NULL");
     SR_REQUIRE(iterations >= 0, "iterations < 0");
     SR_REQUIRE(p->s[0].S[0], "the plan's matrices were released (simrank_biplan_trim)");
-    int rc = simrank_biplan_reset(p);
+    const int rc = simrank_biplan_reset(p);
     if (rc) return rc;
-    int32_t conv = -1, done = 0;
-    // progress(user, k, converged) as in simrank_plan_run_cb (SimRank.py:289-296): a nonzero return value ends the loop
-    auto tell = [&](int32_t k, int32_t converged) { return progress ? progress(user, k, converged) : 0; };
-    if (iterations > 0 && !(1.0 > eps)) {
-        conv = 0;           // loop index 0 compares the identities with zero matrices: "converged" unless 1 > eps
-        (void)tell(0, 1);
-    } else if (iterations > 0 && tell(0, 0) == 0) {
-        rc = iteration(p, eps, 0, 1);                    // iteration 1
-        if (rc) return rc;
-        for (int32_t k = 1;; ++k) {
-            done = k;
-            if (k == iterations) break;                  // the reference makes no test after its last iteration
-            // iteration k + 1 is queued before the counts of iteration k are known; if they say "converged" it is
-            // not adopted: it wrote the buffers of the iterates before last, the current ones are untouched
-            // (small graphs only, common.h kSpeculateBelow: a long iteration is queued once its predecessor's counts are known)
-            const bool spec = std::max(p->s[0].n, p->s[1].n) < kSpeculateBelow;
-            const int c1_cur = p->s[0].cur, c2_cur = p->s[1].cur;
-            if (spec) {
-                rc = iteration(p, eps, 0, (k + 1) & 1);
-                if (rc) return rc;
-            }
+    struct {
+        simrank_biplan* p;
+        double eps;
+        int queue(int slot) { return iteration(p, eps, 0, slot); }         // (each update moves its side on to the new iterate)
+        int count(int slot, bool* zero) {
             unsigned long long c1 = 0, c2 = 0;
-            rc = read_counts(p, k & 1, &c1, &c2);
-            if (rc) return rc;
-            const bool conv_now = c1 == 0 && c2 == 0;    // SimRank.py:289: both groups
-            const bool stop = !conv_now && tell(k, 0) != 0;
-            if (conv_now || stop) {
-                if (conv_now) {
-                    conv = k;
-                    (void)tell(k, 1);
-                }
-                SR_HIP(hipStreamSynchronize(p->stream));  // (the speculative iteration must not outlive its inputs)
-                p->s[0].cur = c1_cur;
-                p->s[1].cur = c2_cur;
-                break;
-            }
-            if (!spec) {
-                rc = iteration(p, eps, 0, (k + 1) & 1);
-                if (rc) return rc;
-            }
+            const int rcc = read_counts(p, slot, &c1, &c2);
+            *zero = c1 == 0 && c2 == 0;                                    // SimRank.py:289: both groups
+            return rcc;
         }
-    }
+        void adopt() {}
+        int drop() {
+            // back to the iterates the speculative iteration read: it wrote the buffers of the iterates before last, the
+            // current ones are untouched (the caller's closing synchronisation keeps it from outliving its inputs).
+            // Flipping back is right because a queue call that returned 0 flipped each side exactly once (side_update),
+            // and the loop drops only after such a call; an iteration that could end half-way would have to save `cur`.
+            p->s[0].cur ^= 1;
+            p->s[1].cur ^= 1;
+            return SIMRANK_OK;
+        }
+    } ops{p, eps};
+    // (iteration k + 1 before the counts of iteration k on small graphs only, common.h kSpeculateBelow)
+    const LoopResult r = run_loop(ops, iterations, eps, std::max(p->s[0].n, p->s[1].n) < kSpeculateBelow, progress, user);
+    if (r.rc) return r.rc;
     SR_HIP(hipStreamSynchronize(p->stream));
-    p->updates = done;
-    if (updates_done) *updates_done = done;
-    if (converged_at) *converged_at = conv;
+    p->updates = r.done;
+    if (updates_done) *updates_done = r.done;
+    if (converged_at) *converged_at = r.conv;
     return SIMRANK_OK;
 }
 
@@ -420,10 +311,7 @@ int simrank_biplan_result_f64(simrank_biplan* p, int32_t group, double* dst, int
     side_t& a = p->s[group - 1];
     SR_REQUIRE(ld >= a.n, "ld %lld < n", (long long)ld);
     SR_REQUIRE(a.S[0], "the plan's matrices were released (simrank_biplan_trim)");
-    // dst[i][j] = S[inv[i]][inv[j]], full form (mode 0: every element crosses PCIe; asymmetric priors give asymmetric iterates)
-    const int rc = simrank_handback_f64(dst, ld, a.S[a.cur], 32, a.rows_pad, a.n, a.inv, 0, p->stream);
-    (void)hipStreamSynchronize(p->stream);
-    return rc;
+    return side_result_f64(a, dst, ld, p->stream);
 }
 
 int simrank_biplan_rows_f32(simrank_biplan* p, int32_t group, const int32_t* rows, int32_t n_rows, float* dst, int64_t ld) {
@@ -431,53 +319,14 @@ int simrank_biplan_rows_f32(simrank_biplan* p, int32_t group, const int32_t* row
     side_t& a = p->s[group - 1];
     SR_REQUIRE(ld >= a.n, "ld %lld < n", (long long)ld);
     SR_REQUIRE(a.S[0], "the plan's matrices were released (simrank_biplan_trim)");
-    return rows_to_host(a.S[a.cur], a.rows_pad, a.n, a.inv, rows, n_rows, dst, ld, 4, 1.0f, p->stream);
+    return side_rows_f32(a, rows, n_rows, dst, ld, p->stream);
 }
 
 int simrank_biplan_topk(simrank_biplan* p, int32_t group, int32_t k, int32_t exclude_diag, int32_t* idx_host, float* val_host) {
     SR_REQUIRE(p && idx_host && val_host && (group == 1 || group == 2) && k > 0 && k <= 1024, "bad top-k arguments");
     side_t& a = p->s[group - 1];
     SR_REQUIRE(a.S[0], "the plan's matrices were released (simrank_biplan_trim)");
-    const int64_t n = a.n;
-    // as simrank_plan_topk: selected on the panel-blocked matrix in the solver's order, caller's ids reported, the rows
-    // put back into the caller's order on the host
-    int32_t* idx_dev = nullptr;
-    int32_t* ord_dev = nullptr;
-    float* val_dev = nullptr;
-    std::vector<int32_t> ord((size_t)n), idx_s((size_t)n * (size_t)k);
-    std::vector<float> val_s((size_t)n * (size_t)k);
-    hipError_t e = pool_hip_alloc((void**)&idx_dev, size_t(n) * size_t(k) * sizeof(int32_t));
-    if (e == hipSuccess) e = pool_hip_alloc((void**)&val_dev, size_t(n) * size_t(k) * sizeof(float));
-    if (e == hipSuccess) e = pool_hip_alloc((void**)&ord_dev, size_t(n) * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(ord.data(), a.inv, size_t(n) * 4, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-    int rc = SIMRANK_OK;
-    if (e == hipSuccess) {
-        std::vector<int32_t> o((size_t)n);
-        for (int64_t i = 0; i < n; ++i) o[(size_t)ord[(size_t)i]] = (int32_t)i;      // position r holds caller's node o[r]
-        ord.swap(o);
-        e = hipMemcpyAsync(ord_dev, ord.data(), size_t(n) * 4, hipMemcpyHostToDevice, p->stream);
-    }
-    if (e == hipSuccess)
-        rc = simrank_topk_rows_blocked(a.S[a.cur], a.rows_pad, n, n, 0, ord_dev, k, exclude_diag, idx_dev, val_dev, p->stream);
-    if (e == hipSuccess && !rc)
-        e = hipMemcpyAsync(idx_s.data(), idx_dev, size_t(n) * size_t(k) * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess && !rc)
-        e = hipMemcpyAsync(val_s.data(), val_dev, size_t(n) * size_t(k) * sizeof(float), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t e2 = hipStreamSynchronize(p->stream);
-    (void)pool_free(idx_dev); (void)pool_free(val_dev); (void)pool_free(ord_dev);
-    if (e != hipSuccess || e2 != hipSuccess) {
-        set_error("simrank_biplan_topk: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-        (void)hipGetLastError();
-        return SIMRANK_ERR_HIP;
-    }
-    if (rc) return rc;
-    for (int64_t r = 0; r < n; ++r) {
-        const int64_t node = ord[(size_t)r];
-        std::memcpy(idx_host + node * k, idx_s.data() + r * k, size_t(k) * sizeof(int32_t));
-        std::memcpy(val_host + node * k, val_s.data() + r * k, size_t(k) * sizeof(float));
-    }
-    return SIMRANK_OK;
+    return side_topk(a, k, exclude_diag, idx_host, val_host, p->stream, "simrank_biplan_topk");
 }
 
 int simrank_biplan_evidence_u8(simrank_biplan* p, int32_t group, uint8_t* dst, int64_t ld) {
@@ -486,42 +335,19 @@ int simrank_biplan_evidence_u8(simrank_biplan* p, int32_t group, uint8_t* dst, i
     SR_REQUIRE(ld >= a.n, "ld %lld < n", (long long)ld);
     SR_REQUIRE(a.ev, "no evidence counts for group %d (created without evidence, or strict_reference with n1 != n2)", group);
     // the counts that GATE this group's update (strict_reference: Evidence_N1's, position by position, for group 2 as well)
-    uint8_t* tmp = nullptr;
-    SR_HIP(pool_hip_alloc((void**)&tmp, size_t(a.n) * size_t(a.n)));
-    const int rc = simrank_permute_layout(a.ev, 32, a.rows_pad, tmp, a.n, 0, a.n, a.n, a.inv, a.inv, 1, p->stream);
-    hipError_t e = hipSuccess;
-    if (!rc) e = hipMemcpy2DAsync(dst, size_t(ld), tmp, size_t(a.n), size_t(a.n), size_t(a.n), hipMemcpyDeviceToHost, p->stream);
-    const hipError_t e2 = hipStreamSynchronize(p->stream);
-    (void)pool_free(tmp);
-    if (e != hipSuccess || e2 != hipSuccess) {
-        set_error("simrank_biplan_evidence_u8: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-        return SIMRANK_ERR_HIP;
-    }
-    return rc;
+    return side_evidence_u8(a, dst, ld, p->stream, "simrank_biplan_evidence_u8");
 }
 
 int simrank_biplan_get(const simrank_biplan* p, int32_t group, const char* key, int64_t* value) {
     SR_REQUIRE(p && key && value, "NULL argument");
     SR_REQUIRE(group == 1 || group == 2, "group must be 1 or 2");
-    const side_t& a = p->s[group - 1];
-    if (!strcmp(key, "restrict_support")) *value = a.restrict_support;
-    else if (!strcmp(key, "iterate")) *value = (int64_t)(uintptr_t)a.S[a.cur];
-    else if (!strcmp(key, "iterate_layout")) *value = 0;
-    else if (!strcmp(key, "iterate_stride")) *value = a.rows_pad;
-    else if (!strcmp(key, "iterate_rows") || !strcmp(key, "iterate_col_hi")) *value = a.n;
-    else if (!strcmp(key, "iterate_col_lo")) *value = 0;
-    else if (!strcmp(key, "ids")) *value = (int64_t)(uintptr_t)a.ord_dev;
-    else SR_REQUIRE(false, "unknown plan key '%s'", key);
-    return SIMRANK_OK;
+    return side_get(p->s[group - 1], key, value);
 }
 
 int simrank_biplan_trim(simrank_biplan* p) {
     SR_REQUIRE(p, "plan is NULL");
     if (p->stream) SR_HIP(hipStreamSynchronize(p->stream));
-    for (side_t& a : p->s) {
-        (void)pool_free(a.S[0]); (void)pool_free(a.S[1]); (void)pool_free(a.Tt); (void)pool_free(a.prior);
-        a.S[0] = a.S[1] = a.Tt = a.prior = nullptr;
-    }
+    for (side_t& a : p->s) side_trim(a);
     return SIMRANK_OK;
 }
 

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "common.h"
+#include "loop.h"
 
 static_assert(sizeof(ncclUniqueId) == SIMRANK_COMM_ID_BYTES, "RCCL's unique id is SIMRANK_COMM_ID_BYTES long");
 
@@ -1258,36 +1259,26 @@ int simrank_shardplan_run(simrank_shardplan* const* plans, int32_t n_local, int3
     SR_REQUIRE(iterations >= 0, "iterations < 0");
     rc = simrank_shardplan_reset(plans, n_local);
     if (rc) return rc;
-    int32_t conv = -1, done = 0;
-    if (iterations > 0 && !(1.0 > eps)) {
-        conv = 0;           // loop index 0 compares S_0 = I with the zero matrix: "converged" unless 1 > eps
-    } else if (iterations > 0) {
-        rc = update(plans, n_local, eps, 0, 1);
-        if (rc) return rc;
-        for (int32_t k = 1;; ++k) {
-            flip(plans, n_local);                    // S[cur] = result of update k
-            done = k;
-            if (k == iterations) break;              // the reference makes no test after its last update
-            // update k + 1 goes out before the count of update k is known only while a rank's update is short (common.h
-            // kSpeculateBelow, on the rows a rank computes per leg: n / ranks columns of n rows)
-            const bool spec = plans[0]->n / std::max(1, plans[0]->world / 2) < kSpeculateBelow;
-            if (spec) {
-                rc = update(plans, n_local, eps, 0, (k + 1) & 1);
-                if (rc) return rc;
-            }
+    struct {
+        simrank_shardplan* const* plans;
+        int32_t n_local;
+        double eps;
+        int queue(int slot) { return update(plans, n_local, eps, 0, slot); }
+        int count(int slot, bool* zero) {
             unsigned long long c = 0;
-            rc = read_count(plans, n_local, k & 1, &c);           // the same number on every rank
-            if (rc) return rc;
-            if (c == 0) {                            // converged at loop index k; a speculative update is dropped
-                conv = k;
-                break;
-            }
-            if (!spec) {
-                rc = update(plans, n_local, eps, 0, (k + 1) & 1);
-                if (rc) return rc;
-            }
+            const int rcc = read_count(plans, n_local, slot, &c);          // the same number on every rank
+            *zero = c == 0;
+            return rcc;
         }
-    }
+        void adopt() { flip(plans, n_local); }
+        int drop() { return SIMRANK_OK; }       // (it wrote the buffer of the iterate before last)
+    } ops{plans, n_local, eps};
+    // update k + 1 goes out before the count of update k is known only while a rank's update is short (common.h
+    // kSpeculateBelow, on the rows a rank computes per leg: n / ranks columns of n rows)
+    const bool spec = plans[0]->n / std::max(1, plans[0]->world / 2) < kSpeculateBelow;
+    const LoopResult r = run_loop(ops, iterations, eps, spec, nullptr, nullptr);
+    if (r.rc) return r.rc;
+    const int32_t done = r.done, conv = r.conv;
     for (int32_t i = 0; i < n_local; ++i) {
         SR_HIP(hipStreamSynchronize(plans[i]->stream));
         if (plans[i]->xstream) SR_HIP(hipStreamSynchronize(plans[i]->xstream));
@@ -1724,26 +1715,25 @@ int simrank_shardbiplan_run(simrank_shardbiplan* const* bps, int32_t n_local, in
     SR_REQUIRE(iterations >= 0, "iterations < 0");
     int rc = simrank_shardbiplan_reset(bps, n_local);
     if (rc) return rc;
-    int32_t conv = -1, done = 0;
-    if (iterations > 0 && !(1.0 > eps)) {
-        conv = 0;           // loop index 0 compares the identities with zero matrices: "converged" unless 1 > eps
-    } else {
-        // (the counts of a loop body are read before the next one is queued: two exchanges per body set the pace here,
-        // not the host's round trip)
-        for (int32_t k = 0; k < iterations; ++k) {
-            rc = bi_iteration(bps, n_local, eps, 0, k & 1);
-            if (rc) return rc;
-            done = k + 1;
-            if (done == iterations) break;               // the reference makes no test after its last iteration
+    struct {
+        simrank_shardbiplan* const* bps;
+        int32_t n_local;
+        double eps;
+        int queue(int slot) { return bi_iteration(bps, n_local, eps, 0, slot); }   // (each update moves its side on)
+        int count(int slot, bool* zero) {
             unsigned long long c1 = 0, c2 = 0;
-            rc = bi_counts(bps, n_local, k & 1, &c1, &c2);
-            if (rc) return rc;
-            if (c1 == 0 && c2 == 0) {                    // SimRank.py:289: both groups
-                conv = done;
-                break;
-            }
+            const int rcc = bi_counts(bps, n_local, slot, &c1, &c2);
+            *zero = c1 == 0 && c2 == 0;                                            // SimRank.py:289: both groups
+            return rcc;
         }
-    }
+        void adopt() {}
+        int drop() { return SIMRANK_OK; }       // (never called: no speculation here; it would have to move both sides back)
+    } ops{bps, n_local, eps};
+    // (never speculative: the counts of a loop body are read before the next one is queued — two exchanges per body set
+    // the pace here, not the host's round trip)
+    const LoopResult r = run_loop(ops, iterations, eps, false, nullptr, nullptr);
+    if (r.rc) return r.rc;
+    const int32_t done = r.done, conv = r.conv;
     std::vector<simrank_shardplan*> s;
     for (int w = 0; w < 2; ++w) {
         rc = bi_sides(bps, n_local, w, s);

@@ -202,7 +202,9 @@ def test_fit_runs_the_c_level_loops(monkeypatch):
 def test_progress_hooks_of_the_c_loop(ops):
     """simrank_plan_run_cb: on_iteration(k) for every loop index that goes on to an update, on_converged(k) once, in the
     reference's order (SimRank.py:131-135) — with and without the speculative update (N below / above 16384 is decided in
-    C; here: below) — and an exception raised in a hook ends the loop and reaches the caller."""
+    C; here: below) — and an exception raised in a hook ends the loop and reaches the caller.  A speculative update that is
+    dropped (on convergence, or when a hook ends the loop) leaves the iterate of the last adopted update in place: bit for
+    bit what a run of exactly that many updates gives, in both plans."""
     from simrank_amd.engine import BiPlan, Plan
     df = synth.er_directed(300, 0.03, seed=11)
     _, csr = ingest.directed(df, False, "from", "to", "weight")
@@ -213,6 +215,9 @@ def test_progress_hooks_of_the_c_loop(ops):
     assert conv == want["k"] and done == conv
     assert seen == [("it", k) for k in range(conv)] + [("conv", conv)]
     assert_close(plan.result(), want["S"])
+    at_conv = plan.result()
+    plan.run(conv, 0.0)
+    np.testing.assert_array_equal(at_conv, plan.result())
     seen.clear()
     assert plan.run(3, 0.0, on_iteration=lambda k: seen.append(k)) == (3, None)
     assert seen == [0, 1, 2]
@@ -225,7 +230,9 @@ def test_progress_hooks_of_the_c_loop(ops):
             raise KeyError("stop here")
     with pytest.raises(KeyError):
         plan.run(50, 0.0, on_iteration=boom)
+    stopped = plan.result()                                # updates 1 and 2; update 3 was queued and is dropped
     assert plan.run(2, 0.0) == (2, None)                   # the plan is still usable
+    np.testing.assert_array_equal(stopped, plan.result())
     plan.free()
     dfb = bipartite_random(50, 30, 0.2, seed=8)
     _, _, _, _, g12, g21 = ingest.bipartite(dfb, False, "user", "item", "weight")
@@ -235,9 +242,16 @@ def test_progress_hooks_of_the_c_loop(ops):
     done, conv = bp.run(100, 1e-4, on_iteration=lambda k: seen.append(("it", k)), on_converged=lambda k: seen.append(("conv", k)))
     assert conv == wantb["k"]
     assert seen == [("it", k) for k in range(conv)] + [("conv", conv)]
+    at_conv = bp.result()
+    bp.run(conv, 0.0)
+    for got, again in zip(at_conv, bp.result()):
+        np.testing.assert_array_equal(got, again)
     with pytest.raises(KeyError):
         bp.run(50, 0.0, on_iteration=boom)
-    s1, s2 = bp.result()
+    stopped = bp.result()
+    assert bp.run(2, 0.0) == (2, None)
+    for got, again in zip(stopped, bp.result()):
+        np.testing.assert_array_equal(got, again)
     bp.free()
 
 
