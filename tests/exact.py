@@ -1,0 +1,533 @@
+"""Exactly summable operands for the two legs, and their references (no GPU).
+
+Let K be an integer matrix, e_c one exponent per operand column and X[j, c] = K[j, c] * 2^e_c; let the pattern's row scales
+be powers of two (or 0).  If for every pattern row a and column c
+
+    sum_{j in row a} |K[j, c]|  <  2^(m - h)          (m: mantissa width of the format, h: headroom for the epilogue)
+
+then every partial sum of row a's products — any order, any association, in registers, LDS slabs or MFMA accumulators — is
+an integer below 2^m times 2^e_c and therefore representable: a float32 kernel that returns anything but
+rowscale[a] * sum has dropped, duplicated, misplaced or mis-split a term.  Signs may be mixed (the bound is on magnitudes).
+No tolerance is involved anywhere: the float64 NumPy result cast to float32 is THE result, bit for bit.
+
+`summable_operand` builds such an X for any pattern (and refuses to return one that violates the condition),
+`summable_symmetric` builds a symmetric S whose leg-1 AND leg-2 operands satisfy it (so W.(W.S)^T is exactly symmetric and
+exactly summable: what the upper-triangle forms need), `exact_epilogue` is the oracle's epilogue expression with a check
+that no intermediate of any association rounds in float32, `plant_previous` puts differences of exactly eps, eps + one step
+and eps - one step at chosen places, `regular_graph` / `exact_updates` give whole fits whose iterates stay exact.
+"""
+from collections import namedtuple
+
+import numpy as np
+import pandas as pd
+import scipy.sparse as sp
+
+from simrank_amd.ingest import CSR
+
+SENTINEL = np.float32(-7.0e33)          # what padding holds before a launch (no result of these tests is near it)
+SENTINEL_U8 = 0xA5
+
+
+# ---- patterns -------------------------------------------------------------------------------------------------------
+def pow2_rowscale(csr, seed):
+    """The pattern with row scales 2^-k, k in 0..6, about 5 % of them zero (as tests' random_csr has them)."""
+    rng = np.random.default_rng(seed)
+    rs = 2.0 ** -rng.integers(0, 7, size=csr.n_rows).astype(np.float64)
+    rs[rng.random(csr.n_rows) < 0.05] = 0.0
+    return CSR(csr.n_rows, csr.n_cols, csr.rowptr, csr.col, rs)
+
+
+def pattern(csr):
+    """The 0/1 pattern as a scipy int64 CSR matrix."""
+    return sp.csr_matrix((np.ones(csr.col.size, dtype=np.int64), csr.col, csr.rowptr), shape=(csr.n_rows, csr.n_cols))
+
+
+def longest_row(csr):
+    return int(np.diff(csr.rowptr).max()) if csr.n_rows else 0
+
+
+def is_pow2_or_zero(x):
+    m, _ = np.frexp(np.asarray(x, dtype=np.float64))
+    return bool(np.all((m == 0.5) | (m == 0.0)))
+
+
+# ---- the operand ----------------------------------------------------------------------------------------------------
+Operand = namedtuple("Operand", "X K exp used")        # X float64 (exact in the format), K int64, exp int64 [L], budget share
+
+
+def _entry_bits(budget_bits, longest):
+    """Width w of the ordinary entries: longest * 2^w <= half the budget (the other half is for the wide entry and slack)."""
+    w = budget_bits - 1 - int(np.ceil(np.log2(max(1, longest))))
+    assert w >= 1, f"a row of {longest} entries leaves no room in 2^{budget_bits}"
+    return w
+
+
+def summable_operand(csr, L, mantissa=24, headroom=0, seed=0, exponents=(-20, 20)):
+    """-> Operand for `csr` (K rows = csr.n_cols, L columns).  Both signs; one WIDE entry per column, magnitude in
+    [2^(m-h-3), 2^(m-h-2)) with the lowest bit set (so the bf16 hi, mid and lo terms of its split are all non-zero), its row
+    rotating with the column so that every 16-row step and every fragment slot carries some; all other entries as wide as the
+    longest pattern row allows; e_c drawn from `exponents` (inclusive).  The condition of this module's header is asserted
+    in integer arithmetic before anything is returned."""
+    assert is_pow2_or_zero(csr.rowscale), "row scales must be powers of two (pow2_rowscale)"
+    rng = np.random.default_rng(seed)
+    Kr, bits = csr.n_cols, mantissa - headroom
+    assert bits >= 5
+    w = _entry_bits(bits, longest_row(csr))
+    K = rng.integers(1, 2 ** w, size=(Kr, L), dtype=np.int64, endpoint=False)
+    K *= rng.choice(np.array([-1, 1], dtype=np.int64), size=(Kr, L))
+    wide = rng.integers(2 ** (bits - 3), 2 ** (bits - 2), size=L, dtype=np.int64) | 1
+    if bits >= 19:                                       # the bit right below the 8 of hi: mid starts there, lo keeps bit 0
+        wide |= 1 << (bits - 3 - 8)
+    wide *= rng.choice(np.array([-1, 1], dtype=np.int64), size=L)
+    # column c: row c mod 16 of a 16-row step that changes with c, so 16 consecutive columns reach every residue
+    c = np.arange(L)
+    wide_row = (c % 16 + 16 * ((c // 16 * 5 + c) % max(1, Kr // 16))) % Kr if Kr >= 16 else c % Kr
+    K[wide_row, np.arange(L)] = wide
+    exp = rng.integers(exponents[0], exponents[1], size=L, endpoint=True).astype(np.int64)
+    used = check_summable(csr, K, bits)
+    X = np.ldexp(K.astype(np.float64), exp[None, :])
+    return Operand(X, K, exp, used)
+
+
+def check_summable(csr, K, bits):
+    """Asserts sum_{j in row a} |K[j, c]| < 2^bits for every row a and column c (int64: no rounding); -> largest share used."""
+    tot = pattern(csr) @ np.abs(K)                      # int64
+    worst = int(tot.max()) if tot.size else 0
+    assert worst < 2 ** bits, f"operand is not exactly summable: a row sums to {worst} >= 2^{bits}"
+    return worst / 2.0 ** bits
+
+
+def product64(csr, X):
+    """diag(rowscale) . pattern . X in float64 — exact for a summable X (every partial sum is representable in 53 bits)."""
+    rs = np.asarray(csr.rowscale, dtype=np.float64)
+    return rs[:, None] * (pattern(csr).astype(np.float64) @ X)
+
+
+Symmetric = namedtuple("Symmetric", "S Tt KS KT used1 used2")
+
+
+def summable_symmetric(csr, mantissa=24, headroom=0, seed=0, exponent=0):
+    """A symmetric integer S = diag(d) + N (x 2^exponent) for a SQUARE pattern such that both legs of W . S . W^T are exactly
+    summable: leg 1's operand is S, leg 2's is Tt = (W . S)^T, and the product is exactly symmetric — what the upper-triangle
+    forms mirror.  d is wide (one odd value of m-h-3 .. m-h-2 bits per column after leg 1, as summable_operand has them), N is
+    a symmetric matrix of small integers of both signs, so no element of Tt is zero for lack of a term.
+    -> (S, Tt, integer S, integer (pattern . S), budget share of leg 1, of leg 2)."""
+    assert csr.n_rows == csr.n_cols and is_pow2_or_zero(csr.rowscale)
+    n, bits = csr.n_rows, mantissa - headroom
+    rng = np.random.default_rng(seed)
+    longest = longest_row(csr)
+    # leg 2 sums |(P S)[a, j]| over j in row b: <= longest * (|d| + longest * nmax)  -> d gets what a row allows, N the rest
+    wd = _entry_bits(bits, longest) - 1
+    nbits = max(1, min(4, bits - 2 - 2 * int(np.ceil(np.log2(max(1, longest))))))
+    d = rng.integers(2 ** (wd - 1), 2 ** wd, size=n, dtype=np.int64) | 1
+    d *= rng.choice(np.array([-1, 1], dtype=np.int64), size=n)
+    N = rng.integers(-(2 ** nbits) + 1, 2 ** nbits, size=(n, n), dtype=np.int64)
+    N = np.triu(N, 1)
+    N = N + N.T
+    P = pattern(csr)
+    # one diagonal entry in 16 as wide as the budget takes (where it reaches 17 bits, the hi, mid and lo terms of its split
+    # are all non-zero); rows that hold several of them decide how wide that is
+    big = np.arange(n) % 16 == 5
+    mag = rng.random(int(big.sum()))
+    for wb in range(bits - 2, wd, -1):
+        dd = d.copy()
+        dd[big] = ((2 ** (wb - 1) * (1 + mag)).astype(np.int64) | 1 | (1 << max(0, wb - 9))) * np.sign(d[big])
+        KS = N + np.diag(dd)
+        KT = P @ KS                                      # int64 [a, j] = sum_{i in row a} S[i, j]; Tt[j, a] = rs_a * KT[a, j]
+        worst2 = int(np.asarray(np.abs(KT) @ P.T).max())  # [a, b] = sum_{j in row b} |KT[a, j]|
+        if worst2 < 2 ** bits:
+            break
+    else:
+        KS = N + np.diag(d)
+        KT = P @ KS
+        worst2 = int(np.asarray(np.abs(KT) @ P.T).max())
+    assert worst2 < 2 ** bits, f"leg 2 is not exactly summable: {worst2} >= 2^{bits}"
+    used1 = check_summable(csr, KS, bits)
+    S = np.ldexp(KS.astype(np.float64), exponent)
+    rs = np.asarray(csr.rowscale, dtype=np.float64)
+    Tt = (rs[:, None] * np.ldexp(KT.astype(np.float64), exponent)).T.copy()
+    return Symmetric(S, Tt, KS, KT, used1, worst2 / 2.0 ** bits)
+
+
+# ---- the split of fused_dev.h / blockdense.hip, emulated ----------------------------------------------------------
+def split3f(x):
+    """float32 array -> (hi, mid, lo) float32 arrays as the device's split3f makes them: hi = x truncated to its upper 16
+    bits (a bf16), mid = (x - hi) truncated, lo = (x - hi - mid) truncated; hi + mid + lo == x for 24-bit mantissas."""
+    x = np.asarray(x, dtype=np.float32)
+    trunc = lambda v: (v.view(np.uint32) & np.uint32(0xFFFF0000)).view(np.float32)
+    hi = trunc(x)
+    r = (x - hi).astype(np.float32)
+    mid = trunc(r)
+    q = (r - mid).astype(np.float32)
+    lo = trunc(q)
+    return hi, mid, lo
+
+
+# ---- the epilogue ---------------------------------------------------------------------------------------------------
+def _exact32(name, v):
+    assert np.array_equal(v.astype(np.float32).astype(np.float64), v), f"{name} rounds in float32"
+    return v
+
+
+def exact_epilogue(prod, coef=0.5, counts=None, prior=None, lbd=None, diag_col0=0, set_diag=True):
+    """float64 reference of the fused epilogue in the oracle's expression (oracle.update: (1 - lbd) * E * coef * prod +
+    lbd * prior; E * coef * prod; coef * prod), for prod = W . X.  Asserts that every intermediate of every association is
+    unchanged by .astype(float32) — coef * s, coef * s * E, s * E, (1 - lbd) * ..., lbd * prior, the result — so neither
+    a contraction to FMA nor the order of the factors can matter on the device.  The diagonal (row == diag_col0 + column)
+    is 1."""
+    prod = _exact32("the product", np.asarray(prod, dtype=np.float64))
+    new = _exact32("coef * s", coef * prod)
+    if counts is not None:
+        E = 1 - 0.5 ** counts.astype(np.float64)
+        _exact32("E", E)
+        _exact32("s * E", prod * E)
+        new = _exact32("coef * s * E", E * coef * prod)
+    if prior is not None:
+        keep = _exact32("1 - lbd", np.float64(1 - lbd))
+        assert float(np.float32(1.0) - np.float32(lbd)) == float(keep)
+        a = _exact32("(1 - lbd) * coef * s * E", keep * new)
+        if counts is not None:
+            _exact32("(1 - lbd) * E", keep * E)
+            _exact32("(1 - lbd) * E * coef", keep * E * coef)
+            assert np.array_equal((1 - lbd) * E * coef * prod, a)
+        b = _exact32("lbd * prior", lbd * np.asarray(prior, dtype=np.float64))
+        new = _exact32("the blend", a + b)
+    new = new.copy()
+    if set_diag:
+        c = np.arange(new.shape[1])
+        r = diag_col0 + c
+        ok = r < new.shape[0]
+        new[r[ok], c[ok]] = 1.0
+    return new
+
+
+def epilogue_counts(shape, seed, symmetric=False):
+    """Evidence counts from {0, 1, 2, 3, 255} (E = 0, 1/2, 3/4, 7/8 and — 2^-255 is below float32 and float64 alike — 1)."""
+    rng = np.random.default_rng(seed)
+    c = rng.choice(np.array([0, 1, 2, 3, 255], dtype=np.uint8), size=shape)
+    if symmetric:
+        c = np.triu(c) + np.triu(c, 1).T
+    return c.astype(np.uint8)
+
+
+def grid_prior(unit, bits, seed, symmetric=False):
+    """A prior on the operand's grid: integers of both signs below 2^bits times `unit` (the result grid rowscale_a * 2^e_c)."""
+    rng = np.random.default_rng(seed)
+    k = rng.integers(-(2 ** bits) + 1, 2 ** bits, size=unit.shape, dtype=np.int64)
+    if symmetric:
+        k = np.triu(k) + np.triu(k, 1).T
+    return k.astype(np.float64) * unit
+
+
+# ---- ties for the convergence count -------------------------------------------------------------------------------
+Planted = namedtuple("Planted", "previous count kinds")
+
+
+def _is32(v):
+    return float(np.float32(v)) == float(v) and np.isfinite(np.float32(v))
+
+
+def plant_previous(want, eps, places, symmetric=False, fmt=np.float32, only=("on", "above", "below")):
+    """`previous` = want (float32, from the reference) except at `places` [(r, c), ...], where it differs from want by
+    exactly eps ("on"), by eps + one step ("above") or by eps - one step ("below"), the three kinds in turn; a step is the
+    smallest power of two at which all three candidates are representable.  -> (previous, the strict-> count over the whole
+    matrix, the kinds planted).  `symmetric`: (c, r) gets what (r, c) got.  `only`: the kinds to plant (("on", "below"): nothing
+    moved by more than eps, the count is zero)."""
+    want = np.asarray(want, dtype=np.float64)
+    prev = want.copy()
+    m, e = np.frexp(eps)
+    assert m == 0.5, "eps must be a power of two"
+    kinds = []
+    done = set()
+    for i, (r, c) in enumerate(places):
+        if (r, c) in done:
+            continue
+        v = want[r, c]
+        if symmetric:
+            assert want[c, r] == v
+        placed = False
+        for sign in ((1, -1) if i % 2 == 0 else (-1, 1)):
+            step = eps
+            best = None
+            while step > eps * 2.0 ** -30:
+                step /= 2
+                cand = [v + sign * eps, v + sign * (eps + step), v + sign * (eps - step)]
+                if all(float(fmt(x)) == x for x in cand):
+                    best = (step, cand)
+                elif best is not None:
+                    break
+            if best is not None:
+                kind = only[len(kinds) % len(only)]
+                prev[r, c] = best[1][("on", "above", "below").index(kind)]
+                if symmetric:
+                    prev[c, r] = prev[r, c]
+                    done.add((c, r))
+                done.add((r, c))
+                kinds.append(kind)
+                placed = True
+                break
+        assert placed, f"no representable tie at {(r, c)}: value {v!r}, eps {eps!r}"
+    assert set(only) <= set(kinds)
+    count = int((np.abs(want - prev) > eps).sum())
+    return Planted(prev.astype(fmt), count, kinds)
+
+
+def tie_places(rows, cols, panel=32):
+    """Places a count can go wrong at: the diagonal, both triangles, the last row and column, the tail behind the last full
+    panel, a pair of mirrored tiles, the first and last element of a panel."""
+    r_last, c_last = rows - 1, cols - 1
+    sq = min(rows, cols)
+    p = [(0, 0), (sq // 2, sq // 2), (sq - 1, sq - 1),                    # diagonal
+         (1, min(c_last, 5)), (min(r_last, 5), 1),                        # both triangles
+         (r_last, 0), (r_last, c_last // 2), (0, c_last), (r_last // 2, c_last), (r_last, c_last),
+         (2, (c_last // panel) * panel), (3, c_last - (1 if c_last else 0)),   # the tail panel
+         (min(r_last, 3), min(c_last, panel + 2)), (min(r_last, panel + 2), min(c_last, 3)),   # mirrored tiles
+         (min(r_last, 7), 0), (min(r_last, 7), min(c_last, panel - 1)),   # first / last element of a panel
+         (min(r_last, 9), min(c_last, panel)), (min(r_last, 9), min(c_last, 2 * panel - 1))]
+    out = []
+    for rc in p:
+        if rc not in out and 0 <= rc[0] < rows and 0 <= rc[1] < cols:
+            out.append(rc)
+    return out
+
+
+# ---- whole fits -----------------------------------------------------------------------------------------------------
+def regular_graph(n, d, seed):
+    """Edge list (from, to, weight) in which every node has exactly d in-neighbours (d a power of two, none of them
+    itself): every row scale is 1/d, the spread of SimRank++ is exactly 1, and with C = 0.5 the float64 oracle's iterates
+    live on a dyadic grid."""
+    assert d & (d - 1) == 0 and 0 < d < n
+    rng = np.random.default_rng(seed)
+    src = np.empty((n, d), dtype=np.int64)
+    for v in range(n):
+        s = rng.choice(n - 1, size=d, replace=False)
+        src[v] = s + (s >= v)
+    return pd.DataFrame({"from": src.ravel(), "to": np.repeat(np.arange(n, dtype=np.int64), d), "weight": 1.0})
+
+
+def biregular_graph(n1, n2, d1, seed):
+    """Bipartite edge list (user, item, weight): every user has d1 items and every item d2 = n1 * d1 / n2 users, both
+    powers of two (a union of d1 shifted permutations without a repeated pair)."""
+    d2 = n1 * d1 // n2
+    assert n1 * d1 == n2 * d2 and d1 & (d1 - 1) == 0 and d2 & (d2 - 1) == 0
+    rng = np.random.default_rng(seed)
+    pu, pi = rng.permutation(n1), rng.permutation(n2)
+    # user u's k-th item: slot (u * d1 + k) of n1 * d1 slots dealt to the items in turn
+    slots = np.arange(n1 * d1)
+    users, items = pu[slots // d1], pi[slots % n2]
+    df = pd.DataFrame({"user": users, "item": items, "weight": 1.0})
+    assert not df.duplicated(["user", "item"]).any()
+    return df
+
+
+def lowbit_exp(a):
+    """Exponent of the lowest set bit over all non-zero elements (float64 array); None when all are zero."""
+    a = np.asarray(a, dtype=np.float64)
+    a = a[a != 0]
+    if a.size == 0:
+        return None
+    m, e = np.frexp(np.abs(a))
+    mant = (m * 2.0 ** 53).astype(np.int64)              # exact: 53-bit integers
+    tz = np.zeros(mant.shape, dtype=np.int64)
+    low = mant & -mant
+    tz = np.log2(low.astype(np.float64)).astype(np.int64)
+    return int((e.astype(np.int64) - 53 + tz).min())
+
+
+Exact = namedtuple("Exact", "updates grid_bits bits")
+
+
+def _one_update(W, S, C, E, mantissa):
+    """One update new = E * C * W S W^T (diag <- 1) with the bookkeeping of exact_updates: -> (new, -log2 grid, quotient) or
+    None when exactness in float64 itself cannot be vouched for."""
+    rs = W.max(axis=1)
+    assert is_pow2_or_zero(rs) and np.array_equal(W, rs[:, None] * (W != 0))
+    P = sp.csr_matrix((W != 0).astype(np.float64))       # (a few entries per row: the products below cost nothing)
+    c_exp = lowbit_exp(np.float64(C))
+    assert 2.0 ** c_exp == C, "C must be a power of two"
+    sums1 = P @ S                                        # leg 1, unscaled (exact in float64 while the quotient is below 2^53)
+    T = rs[:, None] * sums1
+    sums2 = P @ T.T
+    prod = rs[:, None] * sums2
+    new = C * prod
+    terms = [S, sums1, T, sums2, prod, new]
+    totals = [(P @ np.abs(S)).max(), (P @ np.abs(T.T)).max(), np.abs(new).max(), 1.0]
+    if E is not None:
+        new = E * new
+        terms.append(new)
+    np.fill_diagonal(new, 1.0)
+    # (a bound that does not rest on the float64 results themselves: sums stay on their operands' grid, every scale moves it
+    # by its own exponent — below 2^53 the numbers above are exact, and the measured grid can be trusted)
+    floor = lowbit_exp(S) + 2 * lowbit_exp(rs) + c_exp + (lowbit_exp(E) if E is not None and E.any() else 0)
+    if max(totals) / 2.0 ** floor >= 2.0 ** 53:
+        return None
+    grid = floor if mantissa >= 53 else min(x for x in (lowbit_exp(t) for t in terms) if x is not None)
+    return new, -grid, max(totals) / 2.0 ** grid
+
+
+def exact_updates(W, C=0.5, E=None, mantissa=24, limit=24):
+    """How many updates of S' = E * C * W S W^T (diag <- 1) from S = I stay exact in a format of `mantissa` bits: after each
+    update the coarsest common grid of the terms of both legs and of the epilogue (the lowest set bit over all non-zero
+    terms: the elements of S, of W S unscaled and scaled, of C * prod, E * C * prod) divides the largest total (the largest
+    sum of magnitudes a row of either leg can reach, the largest element); the count stops before that quotient reaches
+    2^mantissa.  -> (updates, -log2 of the grid at the last exact update, bits of the quotient there)."""
+    W = np.asarray(W, dtype=np.float64)
+    S = np.eye(W.shape[0])
+    last = Exact(0, 0, 0)
+    for u in range(1, limit + 1):
+        r = _one_update(W, S, C, E, mantissa)
+        if r is None or r[2] >= 2.0 ** mantissa:
+            break
+        S = r[0]
+        last = Exact(u, r[1], int(np.ceil(np.log2(r[2]))))
+    return last
+
+
+def exact_updates_bipartite(W12, W21, C=0.5, E1=None, E2=None, mantissa=24, limit=24):
+    """The same count for the two-matrix loop (S1 from S2, then S2 from the new S1): both half-updates must stay exact."""
+    W12, W21 = np.asarray(W12, dtype=np.float64), np.asarray(W21, dtype=np.float64)
+    S2 = np.eye(W21.shape[0])
+    last = Exact(0, 0, 0)
+    for u in range(1, limit + 1):
+        r1 = _one_update(W12, S2, C, E1, mantissa)
+        if r1 is None or r1[2] >= 2.0 ** mantissa:
+            break
+        r2 = _one_update(W21, r1[0], C, E2, mantissa)
+        if r2 is None or r2[2] >= 2.0 ** mantissa:
+            break
+        S2 = r2[0]
+        last = Exact(u, max(r1[1], r2[1]), int(np.ceil(np.log2(max(r1[2], r2[2])))))
+    return last
+
+
+def oracle_iterates(W, C, E, updates):
+    """[S_0 = I, S_1, ..., S_updates] by the oracle's update."""
+    from oracle import simrank_oracle as O
+    out = [np.eye(W.shape[0])]
+    for _ in range(updates):
+        out.append(O.update(W, out[-1], C, E))
+    return out
+
+
+def tie_eps(iterates, fmt=np.float32):
+    """-> (U, eps, step) for a loop that is to stop on a tie: U = the last update (of those given) that still moved an
+    element (SimRank++ on a small regular graph reaches its fixed point exactly), eps = max |S_{U-1} - S_{U-2}|, a difference
+    that occurs in the run — the test at loop index U - 1 of `iterations=U` passes only under strict > — and the grid step
+    of those two iterates (eps - step may be 0: then every difference counts)."""
+    U = len(iterates) - 1
+    while U > 2 and not np.any(iterates[U - 1] != iterates[U - 2]):
+        U -= 1
+    a, b = iterates[U - 1], iterates[U - 2]
+    eps = float(np.abs(a - b).max())
+    step = 2.0 ** min(lowbit_exp(a), lowbit_exp(b))
+    assert eps >= step > 0 and float(fmt(eps)) == eps and float(fmt(eps - step)) == eps - step
+    return U, eps, step
+
+
+# ---- the cases of tests/test_gpu_exact_kernels.py (here, so that tests/test_exact_cpu.py can build every operand) --------
+LEG1_FUSED = [(520, 400, 333), (129, 77, 33), (130, 200, 2), (64, 1000, 96), (2100, 2100, 160)]
+LEG1_GATHER = [(300, 257, 100), (64, 64, 64), (5, 5, 5)]
+LEG1_SHARD = [((1024, 1024, 256), 256, 4), ((1024, 1024, 200), 128, 0), ((640, 900, 96), 0, 0), ((2048, 2048, 512), 256, 8),
+              ((1000, 1000, 64), 384, 4)]
+LEG1_UNITS = (300, 6000, 100)
+LEG2_N = [64, 129, 1031, 2100]
+HEADROOM = {"plain": 0, "evidence": 3, "all": 5}        # bits the epilogue needs: x 7/8 takes 3, the blend 2 more
+
+
+def corner_case(M, K, seed, **kw):
+    from tests.test_gpu_kernels import corner_csr
+    return pow2_rowscale(corner_csr(M, K, seed=seed, **kw), seed)
+
+
+def gather_case(M, K, seed):
+    from tests.test_gpu_kernels import random_csr
+    csr = random_csr(M, K, 9, seed=seed, heavy={1: min(K, 200), 3: min(K, 70)} if M > 3 else {})
+    return pow2_rowscale(csr, seed)
+
+
+def star_case():
+    """The star of test_fused_long_rows_go_to_the_matrix_cores_whole: one row references every column."""
+    M = K = 1500
+    rng = np.random.default_rng(4)
+    rows = [np.sort(rng.choice(K, size=3, replace=False)).astype(np.int32) for _ in range(M)]
+    rows[700] = np.arange(K, dtype=np.int32)
+    rows[701] = np.arange(0, K, 3, dtype=np.int32)
+    rowptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    return pow2_rowscale(CSR(M, K, rowptr, np.concatenate(rows), np.ones(M)), 4)
+
+
+def wide_ids_case(K=65537):
+    """More than 65536 operand rows (32-bit ids whatever the knob says), the last columns referenced."""
+    M = 420
+    rng = np.random.default_rng(K)
+    hubs = rng.choice(K - 8, size=60, replace=False)
+    rows = []
+    for a in range(M):
+        c = set(rng.choice(K - 8, size=5, replace=False).tolist())
+        if a < 300:
+            c |= set(hubs[rng.random(60) < 0.3].tolist())
+        if a % 7 == 3:
+            c |= {K - 1}
+        if a % 11 == 2:
+            c |= {K - 2, K - 1}
+        rows.append(np.array(sorted(c), dtype=np.int32))
+    rowptr = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int32)
+    return pow2_rowscale(CSR(M, K, rowptr, np.concatenate(rows), np.ones(M)), K)
+
+
+def leg2_case(n, variant, mantissa=24, seed=None, exponent=0):
+    """-> (csr, Symmetric, counts or None, prior or None, lbd, want float64) of a symmetric leg 2 with the epilogue."""
+    seed = n if seed is None else seed
+    csr = corner_case(n, n, seed, hubs=min(n, 150))
+    h = HEADROOM[variant] if mantissa == 24 else 0
+    sym = summable_symmetric(csr, mantissa=mantissa, headroom=h, seed=seed, exponent=exponent)
+    counts = epilogue_counts((n, n), seed, symmetric=True) if variant != "plain" else None
+    prior = lbd = None
+    if variant == "all":
+        rs = np.where(csr.rowscale > 0, csr.rowscale, 1.0)
+        bits = (mantissa - h - 1) if mantissa == 24 else 8
+        prior = grid_prior(rs[:, None] * rs[None, :] * 2.0 ** exponent, bits, seed + 1, symmetric=True)
+        lbd = 0.25
+    want = exact_epilogue(product64(csr, sym.Tt), 0.5, counts, prior, lbd)
+    assert np.array_equal(want, want.T)
+    return csr, sym, counts, prior, lbd, want
+
+
+# ---- the count on fp16-held matrices (half.hip's header) ------------------------------------------------------------
+def half_spacing(stored):
+    """Half the fp16 spacing at the stored values (float64 array of fp16 numbers): 2^(max(exponent field, 1) - 26)."""
+    bits = np.asarray(stored, dtype=np.float16).view(np.uint16)
+    field = np.maximum((bits >> 10) & 31, 1).astype(np.int64)
+    return np.ldexp(1.0, field - 26)
+
+
+def half_moved(new_stored, old_stored, eps_stored):
+    """The rule of half.hip: an element moved when |new (before rounding) - old (stored)| > eps + half the spacing at old."""
+    return np.abs(new_stored - old_stored) > eps_stored + half_spacing(old_stored)
+
+
+def plant_previous_half(want_stored, eps_stored, places, symmetric=False):
+    """fp16 `previous` (stored units) = want rounded, except at `places`: differences a whole fp16 spacing and more ABOVE
+    the widened eps, a whole spacing and more BELOW it, in turn; the caller plants the tie itself (it needs a new value
+    that lies half a spacing off the fp16 grid: the diagonal).  -> (previous as float64 of fp16 values, kinds)."""
+    want = np.asarray(want_stored, dtype=np.float64)
+    prev = want.astype(np.float16).astype(np.float64)
+    kinds = []
+    for i, (r, c) in enumerate(places):
+        v = want[r, c]
+        kind = ("above", "below")[i % 2]
+        sign = 1.0 if (i // 2) % 2 == 0 else -1.0
+        sp = 2 * float(half_spacing(np.float16(abs(v) + 2 * eps_stored)))       # the spacing where the old value will lie
+        cand = np.float16(v + sign * (eps_stored + 4 * sp if kind == "above" else max(0.0, eps_stored - 4 * sp)))
+        old = float(cand)
+        widened = eps_stored + float(half_spacing(cand))
+        gap = abs(v - old) - widened
+        spo = 2 * float(half_spacing(cand))
+        # (where the spacing exceeds eps, "below" is the rounded value itself: inside the bound by eps at least)
+        assert np.isfinite(old) and (gap >= spo if kind == "above" else gap <= -min(spo, eps_stored)), (r, c, v, old, kind)
+        prev[r, c] = old
+        if symmetric:
+            assert want[c, r] == v
+            prev[c, r] = old
+        kinds.append(kind)
+    return prev, kinds

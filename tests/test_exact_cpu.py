@@ -1,0 +1,199 @@
+"""The exactly summable operands of tests/exact.py, without a GPU: the builder's own assertions on every shape the GPU
+tests use, the emulated bf16 split (a non-zero lo term in every column; one dropped lo term changes the bits of the
+product), the epilogue reference, the planted ties, and the table of exact updates on regular graphs."""
+import numpy as np
+import pytest
+
+from oracle import simrank_oracle as O
+from tests import exact as X
+
+
+_CORNER = X.LEG1_FUSED + [s for s, _, _ in X.LEG1_SHARD]
+
+
+# (the unit-cut shape has rows of thousands of entries: no fp16 budget, and no fp16 test uses it)
+@pytest.mark.parametrize("shape,mantissa,headroom", [(s, m, h) for s in _CORNER for m, h in ((24, 0), (24, 5), (11, 0))]
+                         + [(X.LEG1_UNITS, 24, 0)])
+def test_builder_holds_its_condition_on_every_corner_shape(shape, mantissa, headroom):
+    M, K, L = shape
+    if shape == X.LEG1_UNITS:
+        csr = X.corner_case(M, K, 3, hubs=5500, p_hub=0.6)
+    else:
+        csr = X.corner_case(M, K, M + L, hubs=min(K, 150))
+    op = X.summable_operand(csr, L, mantissa=mantissa, headroom=headroom, seed=L)
+    bits = mantissa - headroom
+    assert 0 < op.used < 1
+    assert (op.K > 0).any() and (op.K < 0).any()                       # both signs
+    tot = X.pattern(csr) @ np.abs(op.K)
+    assert int(tot.max()) < 2 ** bits                                   # the condition, once more, in integers
+    wide = np.abs(op.K).max(axis=0)
+    assert np.all(wide >= 2 ** (bits - 3)) and np.all(wide < 2 ** (bits - 2)) and np.all(wide & 1)
+    fmt = np.float32 if mantissa == 24 else np.float64
+    assert np.array_equal(op.X.astype(fmt).astype(np.float64), op.X)
+    assert op.exp.min() >= -20 and op.exp.max() <= 20
+    # the wide rows walk through every 16-row step's residues (every fragment slot carries some)
+    if L >= 32 and K >= 32:
+        assert len(set((np.abs(op.K).argmax(axis=0) % 16).tolist())) == 16
+
+
+def test_guide_value_of_the_issue():
+    """corner_csr(520, 400): the longest row has 69 entries; 16-bit entries and one 22-bit entry per column."""
+    csr = X.corner_case(520, 400, 520 + 333, hubs=150)
+    assert X.longest_row(csr) == 69
+    op = X.summable_operand(csr, 333, seed=333)
+    rest = np.sort(np.abs(op.K), axis=0)[:-1]
+    assert rest.max() < 2 ** 16 and np.abs(op.K).max() >= 2 ** 21
+    assert 0.2 < op.used < 0.6
+
+
+@pytest.mark.parametrize("case", ["gather", "star", "wide_ids"])
+def test_builder_on_the_other_patterns(case):
+    if case == "gather":
+        for M, K, L in X.LEG1_GATHER:
+            X.summable_operand(X.gather_case(M, K, M + L), L, seed=L)
+    elif case == "star":
+        csr = X.star_case()
+        assert X.longest_row(csr) == 1500
+        X.summable_operand(csr, 257, seed=1)
+    else:
+        X.summable_operand(X.wide_ids_case(), 64, seed=1)
+
+
+def test_builder_refuses_an_operand_that_is_not_summable():
+    csr = X.corner_case(129, 77, 1, hubs=77)
+    op = X.summable_operand(csr, 33, seed=0)
+    K = op.K.copy()
+    K[:, 0] = 2 ** 22                                                    # a row of two such entries passes 2^23, three 2^24
+    with pytest.raises(AssertionError, match="not exactly summable"):
+        X.check_summable(csr, K, 24)
+    with pytest.raises(AssertionError, match="powers of two"):
+        X.summable_operand(X.CSR(csr.n_rows, csr.n_cols, csr.rowptr, csr.col, csr.rowscale * 0.3), 4)
+
+
+@pytest.mark.parametrize("shape", X.LEG1_FUSED[:4])
+def test_split_has_a_lo_term_in_every_column_and_dropping_one_shows(shape):
+    M, K, L = shape
+    csr = X.corner_case(M, K, M + L, hubs=min(K, 150))
+    op = X.summable_operand(csr, L, seed=L)
+    x = op.X.astype(np.float32)
+    hi, mid, lo = X.split3f(x)
+    assert np.array_equal(hi.astype(np.float64) + mid.astype(np.float64) + lo.astype(np.float64), op.X)
+    assert (lo != 0).any(axis=0).all() and (mid != 0).any(axis=0).all()
+    want = X.product64(csr, op.X).astype(np.float32)
+    # drop lo for ONE operand row that a pattern row references: the bits of the product change
+    j = int(np.flatnonzero((lo != 0).any(axis=1) & (np.bincount(csr.col, minlength=K) > 0)
+                           & (np.asarray(X.pattern(csr).T @ (csr.rowscale > 0)) > 0))[0])
+    broken = op.X.copy()
+    broken[j] -= lo[j]
+    got = X.product64(csr, broken).astype(np.float32)
+    assert not np.array_equal(got, want)
+    # ... and so does dropping only the low half of one lo term (what a tolerance of 2e-6 cannot see)
+    c = int(np.flatnonzero(lo[j] != 0)[0])
+    half = op.X.copy()
+    half[j, c] -= np.ldexp(1.0, int(op.exp[c]))                          # the lowest bit of the wide entry
+    assert not np.array_equal(X.product64(csr, half).astype(np.float32), want)
+
+
+@pytest.mark.parametrize("n", X.LEG2_N)
+@pytest.mark.parametrize("variant", ["plain", "evidence", "all"])
+def test_symmetric_case_is_summable_symmetric_and_exact_through_the_epilogue(n, variant):
+    csr, sym, counts, prior, lbd, want = X.leg2_case(n, variant)
+    assert np.array_equal(sym.S, sym.S.T) and 0 < sym.used1 < 1 and 0 < sym.used2 < 1
+    assert (sym.KS > 0).any() and (sym.KS < 0).any()
+    assert np.array_equal(sym.Tt, X.product64(csr, sym.S).T)             # leg 2's operand IS leg 1's exact result
+    assert np.array_equal(want.astype(np.float32).astype(np.float64), want)
+    assert np.array_equal(np.diag(want), np.ones(n))
+    if variant == "plain":
+        hi, mid, lo = X.split3f(sym.Tt.astype(np.float32))
+        assert (lo != 0).any() and (mid != 0).any()
+
+
+def test_fp16_symmetric_case():
+    for n in (64, 129, 520):
+        csr, sym, counts, prior, lbd, want = X.leg2_case(n, "evidence", mantissa=11)
+        assert np.array_equal(sym.Tt.astype(np.float16).astype(np.float64), sym.Tt)
+        assert np.array_equal(sym.S.astype(np.float16).astype(np.float64), sym.S)
+
+
+def test_epilogue_reference_refuses_what_would_round():
+    prod = np.array([[2.0 ** 24 - 1, 3.0], [5.0, 7.0]])
+    X.exact_epilogue(prod, 0.5)
+    with pytest.raises(AssertionError, match="rounds in float32"):
+        X.exact_epilogue(prod, 0.5, counts=np.array([[3, 0], [1, 255]], dtype=np.uint8))
+    got = X.exact_epilogue(np.array([[8.0, 16.0], [24.0, 32.0]]), 0.5, np.array([[3, 0], [1, 255]], dtype=np.uint8),
+                           np.array([[4.0, 4.0], [-8.0, 4.0]]), 0.25)
+    assert np.array_equal(got, [[1.0, 1.0], [0.75 * 6.0 - 2.0, 1.0]])
+    got = X.exact_epilogue(np.array([[8.0, 16.0], [24.0, 32.0]]), 0.5, np.array([[3, 0], [1, 255]], dtype=np.uint8),
+                           diag_col0=1)
+    assert np.array_equal(got, [[3.5, 0.0], [1.0, 16.0]])
+    # the oracle's own expression
+    W = np.array([[0.5, 0.5], [0.0, 1.0]])
+    S = np.array([[1.0, 0.25], [0.25, 1.0]])
+    E = np.array([[0.5, 0.75], [0.75, 0.5]])
+    A = np.array([[4.0, 8.0], [8.0, 4.0]])
+    ours = X.exact_epilogue(W @ S @ W.T, 0.5, np.array([[1, 2], [2, 1]], dtype=np.uint8), A, 0.25)
+    assert np.array_equal(ours, O.update(W, S, 0.5, E, A, 0.25))
+
+
+def test_planted_ties():
+    rng = np.random.default_rng(0)
+    want = (rng.integers(-2 ** 12, 2 ** 12, size=(70, 45)) * 2.0 ** -6).astype(np.float64)
+    places = X.tie_places(70, 45)
+    assert (69, 44) in places and (0, 0) in places and any(r < c for r, c in places) and any(r > c for r, c in places)
+    p = X.plant_previous(want, 2.0 ** -3, places)
+    assert set(p.kinds) == {"on", "above", "below"}
+    d = np.abs(want - p.previous.astype(np.float64))
+    assert p.count == p.kinds.count("above") == int((d > 2.0 ** -3).sum())
+    assert int((d >= 2.0 ** -3).sum()) == p.kinds.count("above") + p.kinds.count("on")     # a >= would count the ties
+    assert int((d > 0).sum()) == len(p.kinds)
+    sq = want[:45, :45]
+    sq = np.triu(sq) + np.triu(sq, 1).T
+    ps = X.plant_previous(sq, 2.0 ** -3, X.tie_places(45, 45), symmetric=True)
+    assert np.array_equal(ps.previous, ps.previous.T) and ps.count > ps.kinds.count("above") // 2
+
+
+_GRAPHS = [(300, 2), (300, 4), (1031, 4), (2100, 8)]
+_PLAIN = {(300, 2): (7, 21), (300, 4): (4, 20), (1031, 4): (4, 20), (2100, 8): (3, 21)}      # updates, bits of the grid
+_PP = {(300, 2): 8, (300, 4): 3, (1031, 4): 3, (2100, 8): 2}                                  # updates ((300, 2): at least)
+
+
+@pytest.mark.parametrize("n,d", _GRAPHS)
+def test_exact_updates_on_regular_graphs(n, d):
+    """The table of the issue: how many updates stay exact in float32 on regular_graph(n, d) with C = 0.5; the iterates the
+    count allows are unchanged by a cast to float32, and the eps of the tie tests is a difference that occurs in the run."""
+    df = X.regular_graph(n, d, seed=n + d)
+    nodes, G = O.directed_graph(df)
+    assert np.array_equal(G.sum(axis=1), np.ones(n)) and np.array_equal(np.unique(G), [0.0, 1.0 / d])
+    assert np.array_equal(O.weight(G), G)                                # spread exactly 1
+    E = O.evidence(G)
+    plain = X.exact_updates(G, 0.5)
+    assert (plain.updates, plain.grid_bits) == _PLAIN[(n, d)] and plain.bits < 24
+    pp = X.exact_updates(G, 0.5, E, limit=8)
+    assert pp.updates == _PP[(n, d)] and pp.bits < 24
+    print(f"regular_graph({n}, {d}): plain {plain}, ++ {pp}")
+    for Ev, r in ((None, plain), (E, pp)):
+        its = X.oracle_iterates(G, 0.5, Ev, r.updates)
+        for S in its:
+            assert np.array_equal(S.astype(np.float32).astype(np.float64), S)
+        U, eps, step = X.tie_eps(its)
+        assert 2 <= U <= r.updates
+        assert np.any(np.abs(its[U - 1] - its[U - 2]) == eps)
+        S, k = O.iterate_directed(G, 0.5, U, eps, E=Ev)
+        assert k == U - 1 and np.array_equal(S, its[U - 1])
+        S, k = O.iterate_directed(G, 0.5, U, eps - step, E=Ev)
+        assert k is None and np.array_equal(S, its[U])
+
+
+def test_exact_updates_in_the_other_formats():
+    df = X.regular_graph(300, 2, seed=302)
+    _, G = O.directed_graph(df)
+    assert X.exact_updates(G, 0.5, mantissa=11).updates == 3            # fp16-held matrices and the fp16 wire
+    assert X.exact_updates(G, 0.5, mantissa=53).updates == 17           # float64: 3 bits an update
+    assert X.exact_updates(G, 0.5, O.evidence(G), mantissa=11).updates >= 2
+
+
+def test_biregular_graph():
+    df = X.biregular_graph(256, 128, 2, seed=1)
+    assert set(df.groupby("user").size()) == {2} and set(df.groupby("item").size()) == {4}
+    *_, G12, G21 = O.bipartite_graph(df)
+    assert np.array_equal(np.unique(G12), [0, 0.5]) and np.array_equal(np.unique(G21), [0, 0.25])

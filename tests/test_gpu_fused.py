@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from simrank_amd.ingest import CSR
-from tests.test_gpu_kernels import corner_csr, dense64, random_csr
+from tests.test_gpu_kernels import corner_csr, count_bracket, dense64, random_csr
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-5
@@ -360,6 +360,8 @@ def test_fused_leg2_epilogue_triangle_and_mirror(ops, n, variant):
         assert np.array_equal(got[:32, 32:], got[32:, :32].T)       # mirrored tiles: same bits
     np.testing.assert_allclose(got, got.T, rtol=2e-6, atol=1e-30)
     assert exact == int((np.abs(got.astype(np.float64) - prev.astype(np.float64)) > 0.05).sum())
+    lo, hi = count_bracket(want, prev, 0.05)                       # ... and the count of the float64 reference, as a bracket
+    assert lo <= exact <= hi, (lo, exact, hi)
     assert (some > 0) == (exact > 0) and 0 < some <= exact
     old, exact0, some0, _, _, _ = _leg2_case(ops, n, variant, seed=n, fuse_sym=0)
     np.testing.assert_allclose(got, old, rtol=2e-6, atol=1e-30)
@@ -378,6 +380,8 @@ def test_fused_leg2_with_32_bit_ids(ops, n, variant):
     assert stats[1] > 0 and stats[3] == 0
     np.testing.assert_allclose(got, want, rtol=RTOL, atol=1e-30)
     assert exact == int((np.abs(got.astype(np.float64) - prev.astype(np.float64)) > 0.05).sum())
+    lo, hi = count_bracket(want, prev, 0.05)
+    assert lo <= exact <= hi, (lo, exact, hi)
     got16, exact16, some16, _, _, stats16 = _leg2_case(ops, n, variant, seed=n, fuse_sym=1)
     assert stats16[3] == 1 and stats16[:3] == stats[:3]
     assert np.array_equal(got, got16)
@@ -392,6 +396,8 @@ def test_fused_leg2_with_split_blocks_and_grouped_units(ops, split):
     np.testing.assert_allclose(got, want, rtol=RTOL, atol=1e-30)
     assert np.array_equal(got[:128, 128:], got[128:, :128].T)
     assert exact == int((np.abs(got.astype(np.float64) - prev.astype(np.float64)) > 0.05).sum()) and 0 < some <= exact
+    lo, hi = count_bracket(want, prev, 0.05)
+    assert lo <= exact <= hi, (lo, exact, hi)
 
 
 def test_fused_leg2_with_split_blocks_and_32_bit_ids(ops):
