@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the nine companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
-``_sets``, ``_neighbors``, ``_profile``, ``_cluster``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
+"""What the ctypes bindings of the ten companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
+``_sets``, ``_neighbors``, ``_profile``, ``_cluster``, ``_rank``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
 the lazy load with the version check, ``check``, and the layout codes of a block of an iterate.  A binding keeps its
 prototypes, structures and host helpers.  No CPU fallback: a missing library is an error.
 """
@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 # the layouts of a block of an iterate ("iterate_layout" of simrank_plan_get & co): one set of codes for every library
-# that reads one, all but f64 (csrc/companion.h asserts it of their headers)
+# that reads one, all but f64 and rank (csrc/companion.h asserts it of their headers)
 PANEL_F32, ROWMAJOR_F32, PANEL_F16, ROWMAJOR_F64 = 0, 1, 2, 3
 
 

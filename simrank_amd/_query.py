@@ -118,6 +118,13 @@ class SolverQueries:
         from . import _sets
         return _sets.run(self._reader(j), ptr, ids, w, k, excl, timing)
 
+    def score_ranks(self, j, ptr, ids, w, excl, tptr, tids, timing=None):
+        """Held-out ranks on side j's iterate (``_rank.run``): the baskets as ``score_sets`` takes them, ``tptr`` /
+        ``tids`` their targets as offsets and node ids of side j -> (score float64, before int64) per target and the
+        candidates (int64) per basket; the score band stays on the device."""
+        from . import _rank
+        return _rank.run(self._reader(j), ptr, ids, w, excl, tptr, tids, timing)
+
     def _close_readers(self):
         folders, self._folders = self._folders or {}, None
         for f in folders.values():

@@ -151,12 +151,17 @@ def _block_exclusions(excl, ids_sorted, whole):
     return out, np.ascontiguousarray(at[hit], dtype=np.int32)
 
 
-def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
+def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, consumer=None):
     """Score the baskets (``ptr`` int64 [n_sets + 1], ``ids`` int32 caller ids, ``w`` float64) on ``reader``'s iterate
     (``_query.Reader``, or the ``_neighbors.NeighborReader`` of a pruned model, whose ``score_band`` fills the band from
     the neighbour lists instead) -> float64 [n_sets, n] in the caller's column order, or with ``k`` (ids int32 [n_sets, k], values
     float64 [n_sets, k]): the k best per basket (score descending, id ascending; id -1 / value 0 past the candidates),
-    ``excl`` = (ptr, ids) of the caller ids that are no candidates.  One band of baskets holds at most
+    ``excl`` = (ptr, ids) of the caller ids that are no candidates.  With ``consumer`` nothing of the band is handed back
+    (-> None): ``excl`` marks the band as it does for a selection, and after the kernels of each band are queued the
+    band stays on the device for ``consumer(q0, m, pieces, stage)``: baskets q0 .. q0 + m - 1, ``pieces`` one (block
+    index, device pointer of the block's [m, cols] float64 piece, cols, device caller ids of its columns or None where
+    they are 0 .. cols - 1) per block with columns, ``stage(name, launch)`` the timing hook; what it queues on the
+    reader's stream is done before the next band overwrites the slab (``_rank.run``).  One band of baskets holds at most
     ``_query.SLAB_BYTES`` on the device; per band one score kernel per column block, then one copy of the band or one
     selection per block with the pieces merged on the host.  ``timing``: a dict that receives the milliseconds of the
     stages (HIP events; serialises them)."""
@@ -164,7 +169,12 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
     lib, ops, n = load(), reader.ops, reader.n
     order = GRID_ORDER if grid_order is None else int(grid_order)
     n_sets = int(ptr.size - 1)
-    if k is None:
+    marked = k is not None or consumer is not None         # the band carries the exclusions and the blocks their ids
+    if consumer is not None:
+        if k is not None:
+            raise ValueError("a consumer takes the band instead of a selection: k must be None")
+        result = None
+    elif k is None:
         result = hostpool.empty_f64(n_sets, n)
     else:
         k = int(min(k, max(1, n)))
@@ -198,7 +208,7 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
         for i, b in enumerate(reader.blocks):
             cmap, ids_sorted = reader._col_map(i)
             xp = xc = cid = None
-            if k is not None:
+            if marked:
                 if excl is not None:
                     bp, bc = _block_exclusions(excl, ids_sorted, whole)
                     xp, xc = put(bp), put(bc if bc.size else np.zeros(1, dtype=np.int32))
@@ -211,7 +221,7 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
             held.extend(idx_dev)
             val_dev = [ops._malloc(8 * band * max(1, kk)) for kk in kks]
             held.extend(val_dev)
-        stitch = None if whole or k is not None else np.empty((band, n), dtype=np.float64)
+        stitch = None if whole or marked else np.empty((band, n), dtype=np.float64)
         for q0 in range(0, n_sets, band):
             m = min(band, n_sets - q0)
             off, pieces = 0, []
@@ -235,8 +245,12 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None):
                     ops.d2h(idx, idx_dev[i])
                     ops.d2h(val, val_dev[i])
                     pieces.append((idx, val))
+                elif consumer is not None:
+                    pieces.append((i, piece, cols, cid))
                 off += m * cols
-            if k is not None:
+            if consumer is not None:
+                consumer(q0, m, pieces, stage)
+            elif k is not None:
                 ops.synchronize()
                 if len(pieces) == 1 and pieces[0][0].shape[1] == k:
                     got = pieces[0]

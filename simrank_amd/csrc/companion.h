@@ -1,6 +1,6 @@
-// What the companion libraries share, and nothing of the main library.  All nine (select, f64, query, foldin, model, sets,
-// neighbors, profile, cluster) take the error plumbing of a C entry point; all but f64 take the layouts a block of an
-// iterate is read in, and what depends on them:
+// What the companion libraries share, and nothing of the main library.  All ten (select, f64, query, foldin, model, sets,
+// neighbors, profile, cluster, rank) take the error plumbing of a C entry point; all but f64 and rank (which reads a
+// float64 score band, not an iterate) take the layouts a block of an iterate is read in, and what depends on them:
 //     one element      Stored<L>, offset_of<L>, load<L>, elem<L>: query, sets, neighbors, model
 //     host checks      check_block: query, sets, neighbors, model;  plan_launch: select, profile, cluster
 //     layout dispatch  with_layout, a runtime layout code as a template argument: all but model's pair dispatch

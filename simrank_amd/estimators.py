@@ -480,6 +480,99 @@ class _KeptModel:
         idx, val = solver.score_sets(src_j, ptr, members, w, k, excl)
         return self._best_frame("node", index.take(ids), src_index, idx, val, keep_rows=np.diff(ptr) > 0)
 
+    @staticmethod
+    def _rank_frame(first, who, index, ptr, tptr, tids, score, before, candidates, live=None):
+        """Long frame (``first``, target, score, rank, candidates), one row per listed target; ``live``: per basket
+        whether it ranks anything at all (a basket that does not has rank 0 and 0 candidates throughout)."""
+        from . import _rank
+        basket = np.repeat(np.arange(tptr.size - 1), np.diff(tptr))
+        rank = _rank.ranks_of(score, before)
+        cand = np.asarray(candidates, dtype=np.int64)[basket]
+        if live is not None:
+            dead = ~np.asarray(live, dtype=bool)[basket]
+            rank[dead], cand[dead] = 0, 0
+        return pd.DataFrame({first: who.take(basket), "target": index.take(tids.astype(np.intp)),
+                             "score": np.asarray(score, dtype=np.float64), "rank": rank, "candidates": cand})
+
+    def rank_sets(self, sets, targets, weights=None, names=None, group=None, exclude="members"):
+        """Held-out ranks: for each basket of ``score_sets`` (``sets``, ``weights``, ``names``, ``group`` and ``exclude`` as
+        there) and each label of ``targets[q]`` (one sequence of labels of fitted nodes per basket; repeats kept, empty
+        lists allowed), where that node comes out in the basket's ranking.
+
+        -> long frame (set, target, score, rank, candidates), one row per listed target in the order given: ``score``
+        (float64) the basket's score of the target, bit for bit ``score_sets``' value, or -inf for an excluded target;
+        ``rank`` (int64, 1-based) the position of the target's row in what ``score_sets(..., top_k=N, exclude=...)`` returns
+        for that basket (score descending, label position ascending), 0 when the target is no candidate (excluded, or
+        scored NaN); ``candidates`` (int64) the number of rows that frame has for the basket.  A target listed twice
+        gets two equal rows.
+
+        The score rows stay on the device: every target's rank is counted there (libsimrank_rank.so, |targets| x N
+        comparisons per basket) and 16 bytes per target cross to the host.  The model is left unchanged."""
+        from . import _rank, _sets
+        solver, j, labels = self._kept(group)
+        index, _ = self._ids(j, labels, [])
+        ptr, ids, w, names, _, excl = _sets.prepare(sets, index, weights=weights, names=names,
+                                                    top_k=max(1, len(index)), exclude=exclude)
+        tptr, tids = _rank.prepare(targets, index, ptr.size - 1)
+        who = pd.RangeIndex(ptr.size - 1) if names is None else pd.Index(names)
+        score, before, candidates = solver.score_ranks(j, ptr, ids, w, excl, tptr, tids)
+        return self._rank_frame("set", who, index, ptr, tptr, tids, score, before, candidates)
+
+    def rank_recommended(self, nodes, targets, group=None, exclude_seen=True):
+        """``rank_sets`` for ``recommend``'s baskets: for each fitted node u of ``group`` (its CSR row with the fit's
+        weights, ``exclude_seen`` as there) and each label of ``targets[i]`` (nodes of the group the basket lives in: the
+        ``neighbor`` column of ``recommend``), the position of that label in ``recommend([u], N)``.
+
+        -> long frame (node, target, score, rank, candidates), one row per listed target.  A node without neighbours
+        gets no rows from ``recommend``: its targets have rank 0 and 0 candidates."""
+        return self._rank_recommended(nodes, targets, group, exclude_seen)[0]
+
+    def _rank_recommended(self, nodes, targets, group, exclude_seen):
+        """(``rank_recommended``'s frame, the offsets of every node's targets in it)"""
+        from . import _foldin, _rank, _sets
+        if self._model is None:
+            self._kept(1)                                   # (raises: no kept model, or released)
+        solver, sides = self._model
+        side = _foldin.side_of(len(sides), group)
+        if not isinstance(exclude_seen, bool):
+            raise ValueError(f"exclude_seen must be True or False, not {exclude_seen!r}")
+        j, labels = sides[side]
+        src_j, src_labels = sides[len(sides) - 1 - side]
+        src_index, _ = self._ids(src_j, src_labels, [])
+        index, ids = self._ids(j, labels, nodes)
+        tptr, tids = _rank.prepare(targets, src_index, ids.size)
+        spec = solver.specs[side]
+        ptr, members, w, excl = _sets.csr_baskets(spec.csr, spec.rowscale, ids, len(sides) == 1, exclude_seen)
+        score, before, candidates = solver.score_ranks(src_j, ptr, members, w, excl, tptr, tids)
+        return self._rank_frame("node", index.take(ids), src_index, ptr, tptr, tids, score, before, candidates,
+                                live=np.diff(ptr) > 0), tptr
+
+    def evaluate(self, nodes, targets, ks=(10,), group=None, exclude_seen=True):
+        """Held-out evaluation of ``recommend``: host arithmetic on ``rank_recommended(nodes, targets, ...)``.  ``ks``: a
+        non-empty sequence of positive ints (ValueError before any device work).
+
+        -> one row per node of ``nodes``, in their order: node, targets (how many were listed), not_candidates (how many
+        of them have rank 0), best_rank (the smallest rank above 0; 0 when there is none), reciprocal_rank (1.0 /
+        best_rank; 0.0 when there is none) and, for each k of ``ks``, ``hits@k``: the number of the node's targets with
+        1 <= rank <= k."""
+        from . import _rank
+        ks = _rank.check_ks(ks)
+        nodes = list(nodes)
+        long, tptr = self._rank_recommended(nodes, targets, group, exclude_seen)
+        rank = long["rank"].to_numpy()
+        n = len(nodes)
+        sizes = np.diff(tptr)
+        basket = np.repeat(np.arange(n), sizes)
+        count = lambda mask: np.bincount(basket[mask], minlength=n).astype(np.int64)
+        best = np.full(n, np.iinfo(np.int64).max, dtype=np.int64)
+        np.minimum.at(best, basket[rank > 0], rank[rank > 0])
+        best[best == np.iinfo(np.int64).max] = 0
+        out = {"node": pd.Index(nodes), "targets": sizes, "not_candidates": count(rank == 0), "best_rank": best,
+               "reciprocal_rank": np.where(best > 0, 1.0 / np.maximum(best, 1), 0.0)}
+        for k in ks:
+            out[f"hits@{k}"] = count((rank >= 1) & (rank <= k))
+        return pd.DataFrame(out)
+
     def _all_sides(self, make):
         self._kept(1)
         solver, sides = self._model
