@@ -17,6 +17,7 @@ import numbers
 import numpy as np
 
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
+from ._driver import Scratch, stage
 from ._profile import edges_f32
 
 VERSION = 1              # SIMRANK_CLUSTER_VERSION of include/simrank_cluster.h
@@ -86,28 +87,19 @@ def roots_blocks(ops, blocks, n: int, ts, timing=None) -> np.ndarray:
     edges = ts if ROWMAJOR_F64 in layouts else edges_f32(ts)
     lib = load()
     got = np.empty(m * n + 1, dtype=np.int32)                # the labels, then the status word
-    edges_dev = parent = out = None
-    try:
-        edges_dev = ops.put(np.ascontiguousarray(edges))
-        parent, out = ops._malloc(4 * m * n), ops._malloc(4 * (m * n + 1))
+    with Scratch(ops) as scratch:
+        edges_dev = scratch.put(edges)
+        parent, out = scratch.malloc(4 * m * n), scratch.malloc(4 * (m * n + 1))
         status = out + 4 * m * n
         check(lib.simrank_cluster_init(parent, n, m, status, ops.stream), "simrank_cluster_init")
-        calls = [lambda b=b: check(lib.simrank_cluster_union(
-            b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], b.get("row_ids"), b.get("col_ids"), edges_dev, m,
-            parent, n, status, ops.stream), "simrank_cluster_union") for b in blocks]
-        calls.append(lambda: check(lib.simrank_cluster_labels(parent, n, m, out, status, ops.stream), "simrank_cluster_labels"))
-        for call in calls:
-            if timing is None:
-                call()
-            else:
-                timing.append(ops.timed(call))
+        for b in blocks:
+            stage(ops, timing, "union_ms", lambda: check(lib.simrank_cluster_union(
+                b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], b.get("row_ids"), b.get("col_ids"), edges_dev, m,
+                parent, n, status, ops.stream), "simrank_cluster_union"))
+        stage(ops, timing, "labels_ms", lambda: check(lib.simrank_cluster_labels(parent, n, m, out, status, ops.stream),
+                                                      "simrank_cluster_labels"))
         ops.d2h(got, out)
         ops.synchronize()
-    finally:
-        ops.synchronize()
-        for ptr in (out, parent, edges_dev):
-            if ptr is not None:
-                ops._free(ptr)
     if got[-1] != 0:
         raise ClusterError(f"the union-find kernels reported status {int(got[-1])} (1: a parent out of order, 2: an "
                            "iteration cap reached): the labels are not to be trusted")

@@ -9,10 +9,13 @@ library or device is an error.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
+from . import _driver
 from ._companion import ROWMAJOR_F64, Companion
+from ._driver import bands, id_lists, join
 
 VERSION = 1              # SIMRANK_FOLDIN_VERSION of include/simrank_foldin.h
 TILE = 32                # SIMRANK_FOLDIN_TILE: new nodes per gather / apply
@@ -85,24 +88,8 @@ def prepare(neighbors, index, *, n_out: int, weighted: bool, has_prior: bool, we
     """The arguments of ``fold_in`` checked and normalised on the host, before any device work.  ``index``: pandas Index
     of the SOURCE side's labels in the dense frame's order.  -> (lists: int32 arrays of source ids, w: float64 [n_new],
     prior: float64 [n_new, n_out] C-contiguous or None, names: list or None, k or None)."""
-    import pandas as pd
     from ._query import check_k
-    if isinstance(neighbors, (str, bytes)) or not hasattr(neighbors, "__len__"):
-        raise ValueError("neighbors must be a sequence with one sequence of labels per new node")
-    lists = []
-    for q, one in enumerate(neighbors):
-        if isinstance(one, (str, bytes)) or not hasattr(one, "__iter__"):
-            raise ValueError(f"neighbors[{q}] must be a sequence of labels, not {one!r}")
-        one = list(one)
-        if not one:
-            lists.append(np.empty(0, dtype=np.int32))
-            continue
-        ids = index.get_indexer(pd.Index(one, dtype=object) if index.dtype == object else pd.Index(one))
-        if (ids < 0).any():
-            raise KeyError(one[int(np.argmax(ids < 0))])
-        if np.unique(ids).size != ids.size:
-            raise ValueError(f"neighbors[{q}] repeats a label: a node has one edge per neighbour (duplicate entries)")
-        lists.append(np.ascontiguousarray(ids, dtype=np.int32))
+    lists = id_lists("neighbors", neighbors, index, unique=True, each="new node")
     n_new = len(lists)
     if weighted:
         if weights is None:
@@ -196,7 +183,6 @@ class Folder:
         float64 [n_new, n_out], or with ``top_k`` (ids int32 [n_new, k], values float64 [n_new, k]) selected on the
         device.  ``timing``: a dict that receives the milliseconds of the stages (HIP events; serialises them)."""
         from . import _query, hostpool
-        from ._query import SLAB_BYTES
         ops, rd, n_out, n_src = self.ops, self.reader, self.n_out, self.n_src
         n_new = len(lists)
         k = None if top_k is None else int(min(top_k, max(1, n_out)))
@@ -206,24 +192,16 @@ class Folder:
             result = (np.full((n_new, k), -1, dtype=np.int32), np.zeros((n_new, k), dtype=np.float64))
         if n_new == 0 or n_out == 0:
             return result
-        band = int(max(TILE, min(-(-n_new // TILE) * TILE, SLAB_BYTES // (8 * n_out) // TILE * TILE)))
+        walk = bands(n_new, 8 * n_out, unit=TILE)             # (bands are whole tiles)
         t_bytes = self.f.simrank_foldin_t_bytes(self.layout, n_src)
         dev, up = self._buf, self._put
-
-        def stage(name, launch):
-            if timing is None:
-                launch()
-            else:
-                timing[name] = timing.get(name, 0.0) + ops.timed(launch)
-
+        stage = functools.partial(_driver.stage, ops, timing)
         try:
             T = dev("T", t_bytes)
             member = dev("member", 4 * n_src) if self.evidence else None
-            slab = dev("slab", 8 * band * n_out)
+            slab = dev("slab", 8 * walk.size * n_out)
             # the lists of every new node, once: offsets, source ids, and the iterate's row positions of those ids
-            ptr = np.zeros(n_new + 1, dtype=np.int64)
-            np.cumsum([a.size for a in lists], out=ptr[1:])
-            ids = np.concatenate(lists).astype(np.int32) if ptr[-1] else np.empty(0, dtype=np.int32)
+            ptr, ids = join(lists)
             ids_dev, pos_dev = up("ids", ids), up("pos", np.ascontiguousarray(rd.inv[ids]))
             w_dev = up("w", np.ascontiguousarray(w, dtype=np.float64))
             # (every tile's offsets from its own first entry, TILE + 1 per tile; bands are whole tiles)
@@ -233,8 +211,7 @@ class Folder:
                 seg = ptr[ti * TILE:min(n_new, (ti + 1) * TILE) + 1]
                 rel[ti, :seg.size] = seg - seg[0]
             rel_dev = up("rel", rel)
-            for q0 in range(0, n_new, band):
-                m = min(band, n_new - q0)
+            for q0, m in walk:
                 prior_dev = up("prior", prior[q0:q0 + m]) if prior is not None else None
                 for t0 in range(q0, q0 + m, TILE):
                     nt = min(TILE, q0 + m - t0)

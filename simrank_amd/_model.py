@@ -18,6 +18,7 @@ import struct
 import numpy as np
 
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
+from ._driver import Scratch, bands, stage
 from ._query import SolverQueries
 
 VERSION = 1              # SIMRANK_MODEL_VERSION of include/simrank_model.h
@@ -111,29 +112,17 @@ def pack_reader(reader, dst: Block, overflow_dev=None, timing=None):
     that receives the kernels' milliseconds (HIP events)."""
     ops, lib, n = reader.ops, load(), reader.n
     identity = np.array_equal(reader.order, np.arange(n, dtype=np.int32))
-    row_map = None if identity else ops.put(reader.inv)
-    held = [] if row_map is None else [row_map]
-    try:
+    with Scratch(ops) as scratch:
+        row_map = None if identity else scratch.put(reader.inv)
         for i, b in enumerate(reader.blocks):
             if not b["cols"]:
                 continue
             cmap, ids = reader._col_map(i)             # (positions within the block sorted by caller id, those ids)
             whole = b["col_lo"] == 0 and b["cols"] == n
-            col_dst = None
-            if not whole:
-                col_dst = ops.put(np.ascontiguousarray(ids, dtype=np.int32))
-                held.append(col_dst)
-            launch = lambda b=b, cmap=cmap, col_dst=col_dst: check(lib.simrank_model_pack(
+            col_dst = None if whole else scratch.put(np.ascontiguousarray(ids, dtype=np.int32))
+            stage(ops, timing, "pack_ms", lambda: check(lib.simrank_model_pack(
                 b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], row_map, col_dst, cmap, b["cols"], dst.ptr,
-                dst.layout, dst.stride, n, n, overflow_dev, ops.stream), "simrank_model_pack")
-            if timing is None:
-                launch()
-            else:
-                timing.append(ops.timed(launch))
-        ops.synchronize()
-    finally:
-        for p in held:
-            ops._free(p)
+                dst.layout, dst.stride, n, n, overflow_dev, ops.stream), "simrank_model_pack"))
 
 
 def storage_of(solver, j=0) -> str:
@@ -152,24 +141,23 @@ def detach(solver, precision=None) -> "DetachedSolver":
         raise ValueError("compact(precision='fp16') narrows f32 models; this one holds float64 (storage_precision='f64'): "
                          "use compact() to keep it")
     ops = next(iter(solver.ops.values()))
-    blocks, count_dev = [], None
+    blocks, got = [], np.zeros(1, dtype=np.int64)
     try:
-        overflow = 0
-        for j in sides:
-            want = "fp16" if precision == "fp16" else have[j]
-            dst = Block(ops, want, solver.n[j])
-            blocks.append(dst)
-            if want != have[j]:
-                if count_dev is None:
-                    count_dev = ops.put(np.zeros(1, dtype=np.int64))
-                pack_reader(solver._reader(j), dst, count_dev)
-            else:
-                pack_reader(solver._reader(j), dst)
-        if count_dev is not None:
-            got = np.zeros(1, dtype=np.int64)
-            ops.d2h(got, count_dev)
-            ops.synchronize()
-            overflow = int(got[0])
+        with Scratch(ops) as scratch:
+            count_dev = None                             # (the values binary16 cannot hold, counted over the sides)
+            for j in sides:
+                want = "fp16" if precision == "fp16" else have[j]
+                dst = Block(ops, want, solver.n[j])
+                blocks.append(dst)
+                if want != have[j]:
+                    if count_dev is None:
+                        count_dev = scratch.put(got)
+                    pack_reader(solver._reader(j), dst, count_dev)
+                else:
+                    pack_reader(solver._reader(j), dst)
+            if count_dev is not None:
+                ops.d2h(got, count_dev)
+        overflow = int(got[0])
         if overflow:
             raise ValueError(f"compact(precision='fp16'): {overflow} values do not fit the fp16-held form (value x 2^14 in "
                              f"binary16: magnitudes up to 3.998); the model is unchanged")
@@ -177,9 +165,6 @@ def detach(solver, precision=None) -> "DetachedSolver":
         for b in blocks:
             b.free()
         raise
-    finally:
-        if count_dev is not None:
-            ops._free(count_dev)
     specs = [dataclasses.replace(s, apriori=None if s.apriori is None else _HAS_PRIOR) for s in solver.specs]
     return DetachedSolver(ops, specs, blocks, mode=getattr(solver, "mode", "sparse"), fitted=solver)
 
@@ -234,14 +219,12 @@ class DetachedSolver(SolverQueries):
         b = self._block(j)
         if b.layout != ROWMAJOR_F64:
             return _pairs_above(Selection(self.ops[0], [b.describe()], t), max_pairs)
-        from ._query import SLAB_BYTES
         from ._select import too_many
         n, reader = b.n, self._reader(j)
         offsets = np.zeros(n + 1, dtype=np.int64)
         ids, vals, total = [], [], 0
-        band = int(max(1, min(n, SLAB_BYTES // (8 * max(1, n)))))
-        for r0 in range(0, n, band):
-            rows = np.arange(r0, min(n, r0 + band), dtype=np.int32)
+        for r0, m in bands(n, 8 * max(1, n)):
+            rows = np.arange(r0, r0 + m, dtype=np.int32)
             got = reader.rows(rows)
             hit = got >= float(t)
             hit[np.arange(rows.size), rows] = False

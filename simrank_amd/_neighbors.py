@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from ._companion import Companion
+from ._driver import Scratch, bands, stage
 from ._query import SolverQueries, check_k
 
 VERSION = 1              # SIMRANK_NEIGHBORS_VERSION of include/simrank_neighbors.h
@@ -127,28 +128,19 @@ def select(reader, k: int, timing=None) -> Tables:
     assert b["cols"] == n and b.get("col_lo", 0) == 0
     k = clamp_k(k, n)
     t = Tables(ops, n, k)
-    held = []
     try:
         if n:
             nodes = np.arange(n, dtype=np.int32)
-            pos_dev, ids_dev = ops.put(reader.inv[nodes]), ops.put(nodes)
-            held += [pos_dev, ids_dev]
-            launch = lambda: check(load().simrank_neighbors_select(
-                b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev, ids_dev, n, b.get("col_ids"), k, t.ids,
-                t.vals, ops.stream), "simrank_neighbors_select")
-            if timing is None:
-                launch()
-            else:
-                timing.append(ops.timed(launch))
-            ops.synchronize()
-            ops.h2d(t.diag, np.ascontiguousarray(reader.pair_values(nodes, nodes)))
-            ops.synchronize()
+            with Scratch(ops) as scratch:
+                pos_dev, ids_dev = scratch.put(reader.inv[nodes]), scratch.put(nodes)
+                stage(ops, timing, "select_ms", lambda: check(load().simrank_neighbors_select(
+                    b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev, ids_dev, n, b.get("col_ids"), k,
+                    t.ids, t.vals, ops.stream), "simrank_neighbors_select"))
+                ops.synchronize()
+                ops.h2d(t.diag, np.ascontiguousarray(reader.pair_values(nodes, nodes)))
     except Exception:
         t.free()
         raise
-    finally:
-        for p in held:
-            ops._free(p)
     return t
 
 
@@ -177,7 +169,7 @@ class NeighborReader:
 
     def rows(self, node_ids, out=None, timing=None):
         """float64 [len(node_ids), n]: those rows of P, in bands of at most ``_query.SLAB_BYTES`` on the device."""
-        from . import _query, hostpool
+        from . import hostpool
         ops, n = self.ops, self.n
         node_ids = np.ascontiguousarray(node_ids, dtype=np.int32)
         n_q = int(node_ids.size)
@@ -186,25 +178,15 @@ class NeighborReader:
         if n_q == 0 or n == 0:
             return out
         tables = self._tables()
-        chunks = -(-n // CHUNK)
-        band = int(max(1, min(n_q, _query.SLAB_BYTES // (8 * n), MAX_BLOCKS // chunks)))
-        pos_dev = ops.put(node_ids)
-        slab = ops._malloc(8 * band * n)
-        try:
-            for q0 in range(0, n_q, band):
-                m = min(band, n_q - q0)
-                launch = lambda: check(self.q.simrank_neighbors_rows(*tables, pos_dev + 4 * q0, m, slab, n, ops.stream),
-                                       "simrank_neighbors_rows")
-                if timing is None:
-                    launch()
-                else:
-                    timing.append(ops.timed(launch))
+        walk = bands(n_q, 8 * n, MAX_BLOCKS // -(-n // CHUNK))
+        with Scratch(ops) as scratch:
+            pos_dev = scratch.put(node_ids)
+            slab = scratch.malloc(8 * walk.size * n)
+            for q0, m in walk:
+                stage(ops, timing, "rows_ms", lambda: check(self.q.simrank_neighbors_rows(
+                    *tables, pos_dev + 4 * q0, m, slab, n, ops.stream), "simrank_neighbors_rows"))
                 ops.d2h(out[q0:q0 + m], slab, 8 * m * n)
             ops.synchronize()
-        finally:
-            ops.synchronize()
-            ops._free(slab)
-            ops._free(pos_dev)
         return out
 
     def pair_values(self, a_ids, b_ids):
@@ -216,16 +198,12 @@ class NeighborReader:
         if a.size == 0:
             return out
         tables = self._tables()
-        held = [ops.put(a), ops.put(b), ops._malloc(8 * a.size)]
-        try:
-            check(self.q.simrank_neighbors_pairs(*tables, held[0], held[1], a.size, held[2], ops.stream),
+        with Scratch(ops) as scratch:
+            a_dev, b_dev, val_dev = scratch.put(a), scratch.put(b), scratch.malloc(8 * a.size)
+            check(self.q.simrank_neighbors_pairs(*tables, a_dev, b_dev, a.size, val_dev, ops.stream),
                   "simrank_neighbors_pairs")
-            ops.d2h(out, held[2])
+            ops.d2h(out, val_dev)
             ops.synchronize()
-        finally:
-            ops.synchronize()
-            for p in held:
-                ops._free(p)
         return out
 
     def topk_of(self, node_ids, k):

@@ -18,6 +18,7 @@ import numbers
 import numpy as np
 
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
+from ._driver import Scratch, stage
 
 VERSION = 1              # SIMRANK_PROFILE_VERSION of include/simrank_profile.h
 MAX_EDGES = 1024         # SIMRANK_PROFILE_MAX_EDGES: thresholds of one count sweep
@@ -177,22 +178,14 @@ def count_blocks(ops, blocks, ts, timing=None) -> np.ndarray:
     edges = ts[order] if _kind(blocks) == 64 else edges_f32(ts[order])
     lib, m = load(), int(ts.size)
     got = np.zeros(m + 1, dtype=np.uint64)
-    edges_dev, counts_dev = ops.put(np.ascontiguousarray(edges)), ops.put(got)
-    try:
+    with Scratch(ops) as scratch:
+        edges_dev, counts_dev = scratch.put(edges), scratch.put(got)
         for b in blocks:
-            launch = lambda b=b: check(lib.simrank_profile_count(
+            stage(ops, timing, "count_ms", lambda: check(lib.simrank_profile_count(
                 b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], b.get("row_ids"), b.get("col_ids"), edges_dev, m,
-                counts_dev, ops.stream), "simrank_profile_count")
-            if timing is None:
-                launch()
-            else:
-                timing.append(ops.timed(launch))
+                counts_dev, ops.stream), "simrank_profile_count"))
         ops.d2h(got, counts_dev)
         ops.synchronize()
-    finally:
-        ops.synchronize()
-        ops._free(counts_dev)
-        ops._free(edges_dev)
     at_least = np.cumsum(got[::-1].astype(np.int64))[::-1][1:]           # interval j holds the entries with j edges <= v
     out = np.empty(m, dtype=np.int64)
     out[order] = at_least
@@ -205,29 +198,22 @@ def threshold_blocks(ops, blocks, max_pairs: int, timing=None):
     lib, bits = load(), _kind(blocks)
     bins = 1 << max(DIGIT_PLAN[bits])
     host = np.empty(bins + 1, dtype=np.uint64)
-    dev = ops._malloc(8 * (bins + 1))
 
     def sweep(prefix, pbits, d, want_min):
         host[:] = 0
         host[bins] = 2 ** 64 - 1
         ops.h2d(dev, host)
         for b in blocks:
-            launch = lambda b=b: check(lib.simrank_profile_digits(
+            stage(ops, timing, "digits_ms", lambda: check(lib.simrank_profile_digits(
                 b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], b.get("row_ids"), b.get("col_ids"), prefix, pbits,
-                d, dev, dev + 8 * bins if want_min else None, ops.stream), "simrank_profile_digits")
-            if timing is None:
-                launch()
-            else:
-                timing.append(ops.timed(launch))
+                d, dev, dev + 8 * bins if want_min else None, ops.stream), "simrank_profile_digits"))
         ops.d2h(host, dev)
         ops.synchronize()
         return host[:1 << d].copy(), int(host[bins])
 
-    try:
+    with Scratch(ops) as scratch:
+        dev = scratch.malloc(8 * (bins + 1))
         return radix_select(sweep, bits, max_pairs)
-    finally:
-        ops.synchronize()
-        ops._free(dev)
 
 
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------

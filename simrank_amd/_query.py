@@ -11,6 +11,7 @@ import ctypes as C
 import numbers
 
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
+from ._driver import Scratch, bands, scatter_blocks, stage
 
 VERSION = 1              # SIMRANK_QUERY_VERSION of include/simrank_query.h
 
@@ -56,6 +57,8 @@ def merge_topk(pieces, k: int):
     for i, v in pieces:
         if i.ndim != 2 or i.shape != v.shape or i.shape[0] != n_q:
             raise ValueError("every piece is (ids [n_q, k_p], values [n_q, k_p]) over the same n_q rows")
+    if len(pieces) == 1 and pieces[0][0].shape[1] == k:
+        return pieces[0]                                       # (one block's k best are in the order already)
     idx = np.empty((n_q, k), dtype=np.int32)
     val = np.empty((n_q, k), dtype=np.float64)
     P = len(pieces)
@@ -185,39 +188,26 @@ class Reader:
             out = hostpool.empty_f64(n_q, n)
         if n_q == 0 or n == 0:
             return out
-        pos_dev = ops.put(self.inv[node_ids])
         whole = len(self.blocks) == 1
-        band = int(max(1, min(n_q, SLAB_BYTES // (8 * n))))
-        slab = ops._malloc(8 * band * n)
-        stage = None if whole else np.empty((band, n), dtype=np.float64)
-        try:
-            for q0 in range(0, n_q, band):
-                m = min(band, n_q - q0)
+        walk = bands(n_q, 8 * n)
+        with Scratch(ops) as scratch:
+            pos_dev = scratch.put(self.inv[node_ids])
+            slab = scratch.malloc(8 * walk.size * n)
+            staged = None if whole else np.empty((walk.size, n), dtype=np.float64)
+            for q0, m in walk:
                 off = 0
                 for i, b in enumerate(self.blocks):
                     cmap, _ = self._col_map(i)
-                    launch = lambda b=b, cmap=cmap, off=off: check(self.q.simrank_query_rows(
+                    stage(ops, timing, "rows_ms", lambda: check(self.q.simrank_query_rows(
                         b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev + 4 * q0, m, cmap, b["cols"],
-                        slab + 8 * off, b["cols"], ops.stream), "simrank_query_rows")
-                    if timing is None:
-                        launch()
-                    else:
-                        timing.append(ops.timed(launch))
+                        slab + 8 * off, b["cols"], ops.stream), "simrank_query_rows"))
                     off += m * b["cols"]
                 if whole:
                     ops.d2h(out[q0:q0 + m], slab, 8 * m * n)
                 else:
-                    # every block's [m, cols] piece follows the other in the slab; its columns go to their caller ids
-                    ops.d2h(stage, slab, 8 * m * n)
+                    ops.d2h(staged, slab, 8 * m * n)
                     ops.synchronize()
-                    flat, off = stage.reshape(-1), 0
-                    for i, b in enumerate(self.blocks):
-                        out[q0:q0 + m, self._col_map(i)[1]] = flat[off:off + m * b["cols"]].reshape(m, b["cols"])
-                        off += m * b["cols"]
-            ops.synchronize()
-        finally:
-            ops._free(slab)
-            ops._free(pos_dev)
+                    scatter_blocks(out[q0:q0 + m], staged, m, self.blocks, lambda i: self._col_map(i)[1])
         return out
 
     def pair_values(self, a_ids, b_ids):
@@ -230,9 +220,9 @@ class Reader:
         out = np.empty(m, dtype=np.float64)
         if m == 0:
             return out
-        a_dev = ops.put(a)
-        val_dev = ops._malloc(8 * m)
-        try:
+        with Scratch(ops) as scratch:
+            a_dev = scratch.put(a)
+            val_dev = scratch.malloc(8 * m)
             for b in self.blocks:
                 lo = b["col_lo"]
                 mine = np.nonzero((bp >= lo) & (bp < lo + b["cols"]))[0]
@@ -241,22 +231,14 @@ class Reader:
                 if mine.size == m:
                     rows_dev, got = a_dev, out
                 else:
-                    rows_dev, got = ops.put(np.ascontiguousarray(a[mine])), np.empty(mine.size, dtype=np.float64)
-                cols_dev = ops.put(np.ascontiguousarray(bp[mine] - lo))
-                try:
-                    check(self.q.simrank_query_pairs(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], rows_dev,
-                                                     cols_dev, mine.size, val_dev, ops.stream), "simrank_query_pairs")
-                    ops.d2h(got, val_dev)
-                    ops.synchronize()
-                finally:
-                    ops._free(cols_dev)
-                    if rows_dev != a_dev:
-                        ops._free(rows_dev)
+                    rows_dev, got = scratch.put(a[mine]), np.empty(mine.size, dtype=np.float64)
+                cols_dev = scratch.put(bp[mine] - lo)
+                check(self.q.simrank_query_pairs(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], rows_dev,
+                                                 cols_dev, mine.size, val_dev, ops.stream), "simrank_query_pairs")
+                ops.d2h(got, val_dev)
+                ops.synchronize()
                 if got is not out:
                     out[mine] = got
-        finally:
-            ops._free(val_dev)
-            ops._free(a_dev)
         return out
 
     def topk_of(self, node_ids, k):
@@ -269,31 +251,21 @@ class Reader:
         n_q, k = int(node_ids.size), check_k(k)
         if n_q == 0:
             return np.empty((0, k), dtype=np.int32), np.empty((0, k), dtype=np.float64)
-        pos_dev = ops.put(self.inv[node_ids])
-        ids_dev = ops.put(node_ids)
         pieces = []
-        try:
+        with Scratch(ops) as scratch:
+            pos_dev = scratch.put(self.inv[node_ids])
+            ids_dev = scratch.put(node_ids)
             for b in self.blocks:
                 kk = int(min(k, b["cols"]))
                 if kk < 1:
                     continue
                 idx, val = np.empty((n_q, kk), dtype=np.int32), np.empty((n_q, kk), dtype=np.float64)
-                idx_dev, val_dev = ops._malloc(4 * n_q * kk), ops._malloc(8 * n_q * kk)
-                try:
-                    check(self.q.simrank_query_topk(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev,
-                                                    ids_dev, n_q, b["col_ids"], kk, idx_dev, val_dev, ops.stream),
-                          "simrank_query_topk")
-                    ops.d2h(idx, idx_dev)
-                    ops.d2h(val, val_dev)
-                    ops.synchronize()
-                finally:
-                    ops._free(idx_dev)
-                    ops._free(val_dev)
+                idx_dev, val_dev = scratch.malloc(4 * n_q * kk), scratch.malloc(8 * n_q * kk)
+                check(self.q.simrank_query_topk(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], pos_dev,
+                                                ids_dev, n_q, b["col_ids"], kk, idx_dev, val_dev, ops.stream),
+                      "simrank_query_topk")
+                ops.d2h(idx, idx_dev)
+                ops.d2h(val, val_dev)
+                ops.synchronize()
                 pieces.append((idx, val))
-        finally:
-            ops._free(ids_dev)
-            ops._free(pos_dev)
-        if len(pieces) == 1 and pieces[0][0].shape[1] == k:
-            return pieces[0]
         return merge_topk(pieces, k)
-

@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from ._companion import Companion
+from ._driver import Scratch, id_lists, join
 
 VERSION = 1              # SIMRANK_RANK_VERSION of include/simrank_rank.h
 CHUNK = 1024             # SIMRANK_RANK_CHUNK: band columns of one workgroup
@@ -48,8 +49,7 @@ def prepare(targets, index, n_sets: int):
     per basket (``n_sets`` of them), repeats kept, empty lists allowed.  ``index``: pandas Index of the group's labels in
     the dense frame's order.  -> (tptr int64 [n_sets + 1], tids int32: positions in ``index``).  KeyError for an unknown
     label, ValueError for anything else."""
-    from ._sets import _id_lists
-    tptr, tids = _id_lists("targets", targets, index)
+    tptr, tids = join(id_lists("targets", targets, index))
     if tptr.size - 1 != n_sets:
         raise ValueError(f"targets must have one sequence of labels per basket ({n_sets}), not {tptr.size - 1}")
     return tptr, tids
@@ -99,13 +99,8 @@ def run(reader, ptr, ids, w, excl, tptr, tids, timing=None):
     if n_t == 0 or reader.n == 0:
         return score, before, candidates
     whole = len(reader.blocks) == 1
-    held = []
-
-    def put(host):
-        held.append(ops.put(np.ascontiguousarray(host)))
-        return held[-1]
-
-    try:
+    with Scratch(ops) as scratch:
+        put = scratch.put
         tptr_dev = put(tptr.astype(np.int64, copy=False))
         tid_dev = put(tids.astype(np.int32, copy=False))
         score_dev, before_dev, cand_dev = put(score), put(before), put(candidates)
@@ -127,8 +122,4 @@ def run(reader, ptr, ids, w, excl, tptr, tids, timing=None):
         ops.d2h(before, before_dev)
         ops.d2h(candidates, cand_dev)
         ops.synchronize()
-    finally:
-        ops.synchronize()
-        for p in held:
-            ops._free(p)
     return score, before, candidates

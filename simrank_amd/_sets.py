@@ -10,10 +10,13 @@ the dense rows or the k best of each.  No CPU fallback: a missing library or dev
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
 from ._companion import Companion
+from . import _driver
+from ._driver import Scratch, bands, id_lists, join, scatter_blocks
 
 VERSION = 1              # SIMRANK_SETS_VERSION of include/simrank_sets.h
 CHUNK = 1024             # SIMRANK_SETS_CHUNK: output columns of one workgroup
@@ -46,30 +49,7 @@ LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.ch
 def _id_lists(what, seqs, index):
     """``seqs``: one sequence of labels per basket -> (offsets int64 [n + 1], ids int32): positions in ``index``, in the
     order given, repeats kept.  KeyError for an unknown label."""
-    import pandas as pd
-    if isinstance(seqs, (str, bytes)) or not hasattr(seqs, "__len__"):
-        raise ValueError(f"{what} must be a sequence with one sequence of labels per basket")
-    lists = []
-    for q, one in enumerate(seqs):
-        if isinstance(one, (str, bytes)) or not hasattr(one, "__iter__"):
-            raise ValueError(f"{what}[{q}] must be a sequence of labels, not {one!r}")
-        one = list(one)
-        if not one:
-            lists.append(np.empty(0, dtype=np.int32))
-            continue
-        ids = index.get_indexer(pd.Index(one, dtype=object) if index.dtype == object else pd.Index(one))
-        if (ids < 0).any():
-            raise KeyError(one[int(np.argmax(ids < 0))])
-        lists.append(np.ascontiguousarray(ids, dtype=np.int32))
-    return join(lists)
-
-
-def join(lists):
-    """Arrays of ids -> (offsets int64 [n + 1], ids int32)."""
-    ptr = np.zeros(len(lists) + 1, dtype=np.int64)
-    np.cumsum([a.size for a in lists], out=ptr[1:])
-    ids = np.concatenate(lists).astype(np.int32, copy=False) if ptr[-1] else np.empty(0, dtype=np.int32)
-    return ptr, np.ascontiguousarray(ids)
+    return join(id_lists(what, seqs, index))
 
 
 def check_top_k(top_k, n: int):
@@ -183,24 +163,12 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
         return result
     # a band's workgroups on one block, in either grid order: at most band * max(8, chunks + 7)
     per_basket = max(8, -(-max(b["cols"] for b in reader.blocks) // CHUNK) + 7)
-    band = int(max(1, min(n_sets, _query.SLAB_BYTES // (8 * n), MAX_BLOCKS // per_basket)))
+    walk = bands(n_sets, 8 * n, MAX_BLOCKS // per_basket)
     whole = len(reader.blocks) == 1
     score_band = getattr(reader, "score_band", None)
-    held = []
-
-    def put(host):
-        held.append(ops.put(np.ascontiguousarray(host)))
-        return held[-1]
-
-    def stage(name, launch):
-        if timing is None:
-            launch()
-        else:
-            timing[name] = timing.get(name, 0.0) + ops.timed(launch)
-
-    try:
-        slab = ops._malloc(8 * band * n)
-        held.append(slab)
+    stage = functools.partial(_driver.stage, ops, timing)
+    with Scratch(ops) as scratch:
+        slab, put = scratch.malloc(8 * walk.size * n), scratch.put
         ptr_dev = put(ptr.astype(np.int64, copy=False))
         pos_dev = put(reader.inv[ids]) if ids.size else None
         w_dev = put(np.asarray(w, dtype=np.float64)) if ids.size else None
@@ -217,13 +185,10 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
             per_block.append((b, cmap, ids_sorted, xp, xc, cid))
         if k is not None:
             kks = [int(min(k, b["cols"])) for b in reader.blocks]
-            idx_dev = [ops._malloc(4 * band * max(1, kk)) for kk in kks]
-            held.extend(idx_dev)
-            val_dev = [ops._malloc(8 * band * max(1, kk)) for kk in kks]
-            held.extend(val_dev)
-        stitch = None if whole or marked else np.empty((band, n), dtype=np.float64)
-        for q0 in range(0, n_sets, band):
-            m = min(band, n_sets - q0)
+            idx_dev = [scratch.malloc(4 * walk.size * max(1, kk)) for kk in kks]
+            val_dev = [scratch.malloc(8 * walk.size * max(1, kk)) for kk in kks]
+        stitch = None if whole or marked else np.empty((walk.size, n), dtype=np.float64)
+        for q0, m in walk:
             off, pieces = 0, []
             for i, (b, cmap, ids_sorted, xp, xc, cid) in enumerate(per_block):
                 cols = b["cols"]
@@ -252,24 +217,12 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
                 consumer(q0, m, pieces, stage)
             elif k is not None:
                 ops.synchronize()
-                if len(pieces) == 1 and pieces[0][0].shape[1] == k:
-                    got = pieces[0]
-                else:
-                    got = _query.merge_topk(pieces, k)
-                result[0][q0:q0 + m], result[1][q0:q0 + m] = got
+                result[0][q0:q0 + m], result[1][q0:q0 + m] = _query.merge_topk(pieces, k)
             elif whole:
                 ops.d2h(result[q0:q0 + m], slab, 8 * m * n)
             else:
-                # every block's [m, cols] piece follows the other in the slab; its columns go to their caller ids
                 ops.d2h(stitch, slab, 8 * m * n)
                 ops.synchronize()
-                flat, off = stitch.reshape(-1), 0
-                for b, _, ids_sorted, *_ in per_block:
-                    result[q0:q0 + m, ids_sorted] = flat[off:off + m * b["cols"]].reshape(m, b["cols"])
-                    off += m * b["cols"]
+                scatter_blocks(result[q0:q0 + m], stitch, m, reader.blocks, lambda i: per_block[i][2])
         ops.synchronize()
-    finally:
-        ops.synchronize()
-        for p in held:
-            ops._free(p)
     return result
