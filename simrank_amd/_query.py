@@ -70,6 +70,11 @@ def merge_topk(pieces, k: int):
     return idx, val
 
 
+def clamp_k(n, k, exclude_diag=True) -> int:
+    """The k a top-k of ``n`` nodes is cut to: no more than the candidates of a node, at least one."""
+    return int(min(k, max(1, n - (1 if exclude_diag else 0))))
+
+
 class SolverQueries:
     """What a kept solver (``cplan.PlanSolver``, ``cshard.CShardSolver``, ``cdouble.F64Solver``) answers node queries
     with: one ``Reader`` per side, made on first use by the solver's ``_make_reader(j)`` and closed at ``release``."""
@@ -95,8 +100,7 @@ class SolverQueries:
     def topk_of(self, j, node_ids, k):
         """(ids int32 [len(node_ids), k], values float64): the k most similar OTHER nodes of those nodes, k clamped as
         the solver's ``topk`` clamps it."""
-        k = int(min(k, max(1, self.n[j] - 1)))
-        return self._reader(j).topk_of(node_ids, k)
+        return self._reader(j).topk_of(node_ids, clamp_k(self.n[j], k))
 
     def fold_in(self, j, lists, w, prior=None, top_k=None, timing=None):
         """Rows of NEW nodes joining side j (``_foldin.Folder.run``): ``lists`` hold ids of the side the update reads

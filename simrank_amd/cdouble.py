@@ -16,9 +16,8 @@ import ctypes as C
 import numpy as np
 
 from . import _f64, hostpool
-from ._query import SolverQueries
 from ._f64 import F64MemoryError, check
-from .driver import prior_matrix
+from .driver import Solver, prior_matrix
 
 
 def refusal(world, specs, mode, ops_factory) -> str | None:
@@ -147,30 +146,16 @@ class F64Plan:
             pass
 
 
-class F64Solver(SolverQueries):
+class F64Solver(Solver):
     """``cplan.PlanSolver``'s surface over an ``F64Plan``."""
-
-    mode = "sparse"
 
     def __init__(self, ops, world, specs):
         from .engine import HipOps
-        self.world = world
+        self._describe(world, specs)
         self.ops = {0: ops}
-        self.specs = specs
-        self.bipartite = len(specs) == 2
-        self.n = [s.csr.n_rows for s in specs]
-        self.broadcast_error = None
         self.plan = None
         self._counts = {}                        # id(csr) -> (csr, u8 Matrix): what gates the updates
         priors = [prior_matrix(s, np.float64) for s in specs]
-        if self.bipartite:
-            a, b = specs
-            strict = a.evidence_from is not None and b.evidence_from is a.csr       # quirk Q2: Evidence_N1 on both
-            if strict and self.n[0] != self.n[1] and self.n[0] != 1:
-                # NumPy raises when the first group-2 update RUNS (SimRank.py:423, :491), not at set-up
-                self.broadcast_error = ValueError(
-                    f"operands could not be broadcast together with shapes "
-                    f"({self.n[0]},{self.n[0]}) ({self.n[1]},{self.n[1]}) ")
         patterns = []
         for s in specs:
             e = s.evidence_from
@@ -223,10 +208,7 @@ class F64Solver(SolverQueries):
         update k (index 0: S_0 = I against the zero matrix, "converged" unless 1 > eps), then goes on to update k + 1.
         Returns k, or None when ``iterations`` updates were applied."""
         self.plan.reset()
-        if self.broadcast_error is not None and iterations > 0 and 1.0 > eps:
-            if on_iteration:
-                on_iteration(0)                 # (the reference has printed its first progress line and updated S1)
-            raise self.broadcast_error
+        self._refuse_run(iterations, eps, on_iteration)
         if iterations > 0 and not (1.0 > eps):
             if on_converged:
                 on_converged(0)
@@ -245,9 +227,7 @@ class F64Solver(SolverQueries):
         return self.plan.result(j)
 
     def topk(self, j, k, exclude_diag=True):
-        n = self.n[j]
-        k = int(min(k, max(1, n - (1 if exclude_diag else 0))))
-        return self.plan.topk(j, k, exclude_diag)
+        return self.plan.topk(j, self._k(j, k, exclude_diag), exclude_diag)
 
     def pairs(self, j, t, max_pairs):
         """Side j's pairs at least ``t`` similar (float64 comparison), selected on the device: (offsets [n + 1],

@@ -21,8 +21,7 @@ import os
 
 import numpy as np
 
-from ._query import SolverQueries
-from .driver import LocalWorld, TorchWorld, prior_matrix
+from .driver import LocalWorld, Solver, TorchWorld, pattern_refusal, prior_matrix
 
 
 def applies(world, specs, mode) -> str | None:
@@ -39,20 +38,11 @@ def applies(world, specs, mode) -> str | None:
     if isinstance(world, TorchWorld) and world.dist.get_backend(world.group) != "nccl":
         return "the sharded C loop exchanges over RCCL (one GPU per process)"
     if len(specs) == 2:
-        a, b = specs
-        if fp16:
-            return "the bipartite classes keep fp16-held matrices to one GPU"
-        if (a.evidence_from is None) != (b.evidence_from is None):
-            return "evidence on one group only"
-        if a.evidence_from is not None and (a.evidence_from is not a.csr or
-                                            not (b.evidence_from is a.csr or b.evidence_from is b.csr)):
-            return "evidence of a foreign pattern"
-        if a.csr.n_rows != b.csr.n_cols or a.csr.n_cols != b.csr.n_rows or a.csr.nnz != b.csr.nnz:
-            return "the two patterns are not each other's transpose"
-        return None
+        return "the bipartite classes keep fp16-held matrices to one GPU" if fp16 else pattern_refusal(specs)
     s = specs[0]
-    if s.evidence_from is not None and s.evidence_from is not s.csr:
-        return "evidence of a foreign pattern"
+    why = pattern_refusal(specs)
+    if why is not None:
+        return why
     if fp16 and s.apriori is not None:
         return "a prior keeps fp16-held matrices to one GPU"
     if fp16 and s.csr.n_rows % (64 * world.size):
@@ -88,22 +78,16 @@ def _rccl_comm(world, ops):
     return comm
 
 
-class CShardSolver(SolverQueries):
+class CShardSolver(Solver):
     """The estimators' view of ``engine.ShardPlans`` / ``engine.ShardBiPlans``: the sharded loops behind the C ABI
     (csrc/shardplan.hip) — every class, f32 (the parity path) or, for SimRank / SimRank++ without a prior, fp16-held
     matrices."""
-
-    mode = "sparse"
 
     def __init__(self, make_ops, world, specs):
         from .engine import ShardBiPlans, ShardPlans
         if not isinstance(specs, (list, tuple)):
             specs = [specs]
-        self.world = world
-        self.specs = specs
-        self.bipartite = len(specs) == 2
-        self.storage = specs[0].storage
-        self.n = [s.csr.n_rows for s in specs]
+        self._describe(world, specs)
         self.ops = {r: make_ops(r) for r in world.local_ranks}
         ops = self.ops[world.local_ranks[0]]
         if self.storage == "fp16" and not getattr(ops, "supports_half_storage", False):
@@ -113,39 +97,25 @@ class CShardSolver(SolverQueries):
         form = -1 if sym == "auto" else (1 if sym else 0)
         if self.storage == "fp16" or not all(s.symmetric for s in specs):
             form = 0                 # (no mirror image to share: fp16-held blocks, asymmetric iterates)
-        common = dict(world=world.size, comm=None if local else _rccl_comm(world, ops),
+        if form == 1 and all(n % (32 * world.size) for n in self.n):
+            form = 0
+        common = dict(world=world.size, comm=None if local else _rccl_comm(world, ops), leg2_form=form,
                       stages=0 if local else getattr(world, "stages", 0),
                       wire_fp16=getattr(world, "exchange_precision", "f32") == "fp16")
-        self.broadcast_error = None
         if self.bipartite:
             a, b = specs
-            evidence = a.evidence_from is not None
-            strict = evidence and b.evidence_from is a.csr              # quirk Q2: Evidence_N1 gates both updates
-            if strict and self.n[0] != self.n[1] and self.n[0] != 1:
-                self.broadcast_error = ValueError(
-                    f"operands could not be broadcast together with shapes "
-                    f"({self.n[0]},{self.n[0]}) ({self.n[1]},{self.n[1]}) ")
-            def fits(n):
-                return n % (32 * world.size) == 0
-            if form == 1 and not (fits(self.n[0]) or fits(self.n[1])):
-                form = 0
-            self.plans = ShardBiPlans(ops, a.csr, a.rowscale, b.rowscale, c1=a.coef, c2=b.coef, evidence=evidence,
+            self.plans = ShardBiPlans(ops, a.csr, a.rowscale, b.rowscale, c1=a.coef, c2=b.coef, evidence=self.gated,
                                       apriori1=prior_matrix(a, np.float32), apriori2=prior_matrix(b, np.float32), lbd1=a.lbd, lbd2=b.lbd,
-                                      strict_reference=strict, leg2_form=form, **common)
+                                      strict_reference=self.strict, **common)
         else:
             (s,) = specs
-            if form == 1 and s.csr.n_rows % (32 * world.size):
-                form = 0
-            self.plans = ShardPlans(ops, s.csr, rowscale=s.rowscale, coef=s.coef, evidence=s.evidence_from is not None,
-                                    apriori=prior_matrix(s, np.float32), lbd=s.lbd, storage=self.storage, leg2_form=form, **common)
+            self.plans = ShardPlans(ops, s.csr, rowscale=s.rowscale, coef=s.coef, evidence=self.gated,
+                                    apriori=prior_matrix(s, np.float32), lbd=s.lbd, storage=self.storage, **common)
         self.root = local or world.rank == 0
 
     def run(self, iterations, eps, on_iteration=None, on_converged=None):
         """The loop of SimRank.py:129-140 / :288-302 (the count of every update is read before the next one is queued)."""
-        if self.broadcast_error is not None and iterations > 0 and 1.0 > eps:
-            if on_iteration:
-                on_iteration(0)
-            raise self.broadcast_error
+        self._refuse_run(iterations, eps, on_iteration)
         self.plans.reset()
         changed = sum(self.n) if 1.0 > eps else 0
         for k in range(iterations):
@@ -165,23 +135,20 @@ class CShardSolver(SolverQueries):
         self.world.dist.broadcast_object_list(box, src=0, group=self.world.group)
         return box[0]
 
-    def result(self, j=0):
-        full = (self.plans.result(j + 1, root=0, i_am_root=self.root) if self.bipartite
-                else self.plans.result(root=0, i_am_root=self.root))
+    def _deliver(self, value):
+        """Root's ``value`` as the world hands results back: to rank 0 alone (the other ranks are told why they hold
+        None), or with ``TorchWorld(handback="all")`` to every rank."""
         if isinstance(self.world, LocalWorld) or getattr(self.world, "handback", "root") == "root":
             if not self.root:
-                import warnings
-                warnings.warn("TorchWorld(handback='root'): only rank 0 receives the similarity matrix, fit() returns "
-                              "None on this rank (pass handback='all', or fit(top_k=k), to get results on every rank)",
-                              RuntimeWarning, stacklevel=4)
-            return full
-        return self._share(full)
+                self._warn_root_only()
+            return value
+        return self._share(value)
+
+    def result(self, j=0):
+        return self._deliver(self.plans.side(j).result(root=0, i_am_root=self.root))
 
     def topk(self, j, k, exclude_diag=True):
-        n = self.n[j]
-        k = int(min(k, max(1, n - (1 if exclude_diag else 0))))
-        idx, val = (self.plans.topk(j + 1, k, exclude_diag, root=0, i_am_root=self.root) if self.bipartite
-                    else self.plans.topk(k, exclude_diag, root=0, i_am_root=self.root))
+        idx, val = self.plans.side(j).topk(self._k(j, k, exclude_diag), exclude_diag, root=0, i_am_root=self.root)
         if not isinstance(self.world, LocalWorld):
             idx, val = self._share((idx, val))
         return idx, val.astype(np.float64)
@@ -191,7 +158,7 @@ class CShardSolver(SolverQueries):
         columns; an in-process group merges them here, an RCCL world agrees on the total (``max_pairs`` is refused on every
         rank alike) and sends the pieces to rank 0, sizes first, which merges them.  Delivered as ``result``."""
         from . import _select
-        sel = self.plans.selection(j + 1, t) if self.bipartite else self.plans.selection(t)
+        sel = self.plans.side(j).selection(t)
         if isinstance(self.world, LocalWorld):
             if sel.total > max_pairs:
                 raise _select.too_many(sel.total, max_pairs)
@@ -205,19 +172,11 @@ class CShardSolver(SolverQueries):
         pieces = [None] * self.world.size if self.root else None
         dist.gather_object(sel.emit(), pieces, dst=dist.get_global_rank(group, 0) if group is not None else 0,
                            group=group)
-        out = _select.merge([p for got in pieces for p in got], sel.row_order) if self.root else None
-        if getattr(self.world, "handback", "root") == "root":
-            if not self.root:
-                import warnings
-                warnings.warn("TorchWorld(handback='root'): only rank 0 receives the similarity matrix, fit() returns "
-                              "None on this rank (pass handback='all', or fit(top_k=k), to get results on every rank)",
-                              RuntimeWarning, stacklevel=4)
-            return out
-        return self._share(out)
+        return self._deliver(_select.merge([p for got in pieces for p in got], sel.row_order) if self.root else None)
 
     def _make_reader(self, j):
         """Node queries on a kept model (``_query.SolverQueries``): libsimrank_query.so on side j's iterate, in place."""
-        return self.plans.reader(j + 1) if self.bipartite else self.plans.reader()
+        return self.plans.side(j).reader()
 
     def release(self):
         self._close_readers()

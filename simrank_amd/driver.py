@@ -23,6 +23,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
+from ._query import SolverQueries, clamp_k
 from .ingest import CSR
 
 
@@ -67,6 +68,67 @@ def prior_matrix(spec: SideSpec, dtype):
     if a.shape != (n, n):
         raise ValueError(f"operands could not be broadcast together with shapes ({n},{n}) {a.shape} ")
     return np.ascontiguousarray(a, dtype=dtype)
+
+
+def pattern_refusal(specs) -> str | None:
+    """None when the patterns of these specs are what the loops behind the C ABI take, else the reason they are not
+    (``cshard.applies`` hands it on, ``cplan.applies`` refuses without one): evidence gates both groups or neither, it
+    is that of a side's own pattern (group 2: or group 1's, quirk Q2), and the two patterns are each other's transpose."""
+    if len(specs) == 2:
+        a, b = specs
+        if (a.evidence_from is None) != (b.evidence_from is None):
+            return "evidence on one group only"
+        if a.evidence_from is not None and (a.evidence_from is not a.csr or
+                                            not (b.evidence_from is a.csr or b.evidence_from is b.csr)):
+            return "evidence of a foreign pattern"
+        if a.csr.n_rows != b.csr.n_cols or a.csr.n_cols != b.csr.n_rows or a.csr.nnz != b.csr.nnz:
+            return "the two patterns are not each other's transpose"
+        return None
+    (s,) = specs
+    if s.evidence_from is not None and s.evidence_from is not s.csr:
+        return "evidence of a foreign pattern"
+    return None
+
+
+class Solver(SolverQueries):
+    """What the solvers over the C loops (``cplan.PlanSolver``, ``cshard.CShardSolver``, ``cdouble.F64Solver``) share:
+    the fields ``estimators.py`` and the kept model read, the reference's strict-evidence quirk and its broadcast error,
+    the clamp of a top-k and the warning of a rank that receives nothing.  A solver's plan object indexes its sides
+    0 | 1 (``engine``'s ``side(j)``, ``F64Plan``'s ``side`` argument), so the query methods need no fork."""
+
+    mode = "sparse"
+
+    def _describe(self, world, specs):
+        self.world, self.specs = world, specs
+        self.bipartite = len(specs) == 2
+        self.n = [s.csr.n_rows for s in specs]
+        self.storage = specs[0].storage
+        a, b = specs[0], specs[-1]
+        self.gated = a.evidence_from is not None                        # evidence gates the updates
+        self.strict = self.bipartite and self.gated and b.evidence_from is a.csr      # quirk Q2: Evidence_N1 gates both
+        self.broadcast_error = None
+        if self.strict and self.n[0] != self.n[1] and self.n[0] != 1:
+            # NumPy raises when the first group-2 update RUNS (SimRank.py:423, :491), not at set-up
+            self.broadcast_error = ValueError(
+                f"operands could not be broadcast together with shapes "
+                f"({self.n[0]},{self.n[0]}) ({self.n[1]},{self.n[1]}) ")
+
+    def _refuse_run(self, iterations, eps, on_iteration):
+        """How ``run`` opens: the reference's broadcast error, where its loop would reach the first group-2 update."""
+        if self.broadcast_error is not None and iterations > 0 and 1.0 > eps:
+            if on_iteration:
+                on_iteration(0)                 # (the reference has printed its first progress line and updated S1)
+            raise self.broadcast_error
+
+    def _k(self, j, k, exclude_diag=True) -> int:
+        return clamp_k(self.n[j], k, exclude_diag)
+
+    def _warn_root_only(self):
+        """From the helper of a hand-back method of the solver: the warning names the frame three above that method."""
+        import warnings
+        warnings.warn("TorchWorld(handback='root'): only rank 0 receives the similarity matrix, fit() returns "
+                      "None on this rank (pass handback='all', or fit(top_k=k), to get results on every rank)",
+                      RuntimeWarning, stacklevel=6)
 
 
 class LocalWorld:

@@ -1,8 +1,10 @@
 """Device layer: thin Python objects over the C ABI (include/simrank_hip.h).
 
-``HipOps`` is the operation set the iteration driver (``driver.py``) is written against:
-allocate / upload / download matrices, upload a graph, and launch the kernels.  It owns
-no algorithm.  It fails loudly when the library or the GPU is missing.
+``HipOps`` is the operation set the kernel-by-kernel Python choreography (``tests/pydriver.py``, a test double) and the
+companion drivers are written against: allocate / upload / download matrices, upload a graph, and launch the kernels.
+It owns no algorithm.  It fails loudly when the library or the GPU is missing.  ``Plan``, ``BiPlan``, ``ShardPlans`` and
+``ShardBiPlans`` wrap the loops behind the C ABI; ``side(j)`` of each is one similarity matrix with one surface
+(``_GpuSide`` / ``_ShardSide``), which the solvers (``cplan.py``, ``cshard.py``) query.
 """
 from __future__ import annotations
 
@@ -13,11 +15,30 @@ import threading
 import numpy as np
 
 from . import _lib, hostpool
+from ._driver import Scratch
 from ._lib import Epilogue, SimRankHipError, check
 from .ingest import CSR
 
 
 CHANGED_SLOTS = 1024      # SIMRANK_CHANGED_SLOTS of include/simrank_hip.h
+
+
+class _Owner:
+    """What owns a handle of the main library: ``free()`` gives ``self.handle`` back once, to the entry point
+    ``_destroy`` of ``ops.lib`` (the sharded classes, which own several, bring their own), and the finaliser calls it."""
+
+    _destroy = None
+
+    def free(self):
+        if self.handle:
+            getattr(self.ops.lib, self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 class Matrix:
@@ -69,7 +90,9 @@ class Matrix:
             pass
 
 
-class Graph:
+class Graph(_Owner):
+    _destroy = "simrank_graph_destroy"
+
     def __init__(self, ops, csr: CSR, rowscale: np.ndarray | None = None, counting=None):
         """``counting`` = (counts Matrix, col0): the evidence counts of the pattern (columns col0 ... of it) are queued as
         soon as the pattern is on the device and run beside the host plan builders (simrank_graph_create_counting)."""
@@ -92,21 +115,49 @@ class Graph:
         self.ops, self.handle = ops, h
         self.n_rows, self.n_cols, self.nnz = csr.n_rows, csr.n_cols, int(col.size)
 
-    def free(self):
-        if self.handle:
-            self.ops.lib.simrank_graph_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
 
 class PlanOptions(C.Structure):                # struct simrank_plan_options
     _fields_ = [("coef", C.c_float), ("lbd", C.c_float), ("apriori", C.c_void_p), ("ld_apriori", C.c_int64),
                 ("evidence", C.c_int32), ("reorder", C.c_int32), ("storage_fp16", C.c_int32), ("dense_terms", C.c_int32)]
+
+
+class ShardPlanOptions(C.Structure):           # struct simrank_shardplan_options
+    _fields_ = [("coef", C.c_float), ("lbd", C.c_float), ("apriori", C.c_void_p), ("ld_apriori", C.c_int64),
+                ("evidence", C.c_int32), ("reorder", C.c_int32), ("leg2_form", C.c_int32), ("stages", C.c_int32),
+                ("wire_fp16", C.c_int32), ("storage_fp16", C.c_int32)]
+
+
+class BiPlanOptions(C.Structure):              # struct simrank_biplan_options
+    _fields_ = [("c1", C.c_float), ("c2", C.c_float), ("lbd1", C.c_float), ("lbd2", C.c_float),
+                ("apriori1", C.c_void_p), ("ld_apriori1", C.c_int64), ("apriori2", C.c_void_p),
+                ("ld_apriori2", C.c_int64), ("evidence", C.c_int32), ("reorder", C.c_int32),
+                ("strict_reference", C.c_int32)]
+
+
+# ---- what the four create calls take: host arrays (the caller keeps what these return until its call is back) ----
+def _csr_args(csr: CSR, *rowscales):
+    """(nnz, rowptr, col or NULL, one pointer per row scale) as int32 / float32 host arrays, and the arrays themselves."""
+    rowptr = np.ascontiguousarray(csr.rowptr, dtype=np.int32)
+    col = np.ascontiguousarray(csr.col, dtype=np.int32)
+    rs = [np.ascontiguousarray(r, dtype=np.float32) for r in rowscales]
+    args = (col.size, rowptr.ctypes.data, col.ctypes.data if col.size else None, *[r.ctypes.data for r in rs])
+    return args, (rowptr, col, rs)
+
+
+def _prior_fields(apriori, tag: str = ""):
+    """The ``apriori<tag>`` / ``ld_apriori<tag>`` fields of an options struct (NULL and 0 without a prior), and the
+    float32 array they point at."""
+    ap = None if apriori is None else np.ascontiguousarray(apriori, dtype=np.float32)
+    fields = {"apriori" + tag: None if ap is None else ap.ctypes.data,
+              "ld_apriori" + tag: 0 if ap is None else ap.shape[1]}
+    return fields, ap
+
+
+def _biplan_options(c1, c2, lbd1, lbd2, apriori1, apriori2, evidence, reorder, strict_reference):
+    f1, a1 = _prior_fields(apriori1, "1")
+    f2, a2 = _prior_fields(apriori2, "2")
+    return BiPlanOptions(c1=c1, c2=c2, lbd1=lbd1, lbd2=lbd2, evidence=int(evidence), reorder=int(reorder),
+                         strict_reference=int(strict_reference), **f1, **f2), (a1, a2)
 
 
 def _progress_callback(on_iteration, on_converged):
@@ -124,6 +175,21 @@ def _progress_callback(on_iteration, on_converged):
             raised.append(e)
             return 1
     return _lib.PROGRESS_FN(hook), raised
+
+
+def _run(lib, name, head, iterations, eps, on_iteration=None, on_converged=None):
+    """``name``(*head, iterations, eps, &done, &converged), or with a hook its ``_cb`` form, whose hooks are called from
+    inside the C loop -> (updates applied, loop index at which the convergence test passed or None)."""
+    done, conv = C.c_int32(0), C.c_int32(-1)
+    if on_iteration is None and on_converged is None:
+        check(getattr(lib, name)(*head, int(iterations), float(eps), C.byref(done), C.byref(conv)), name)
+    else:
+        cb, raised = _progress_callback(on_iteration, on_converged)
+        check(getattr(lib, name + "_cb")(*head, int(iterations), float(eps), cb, None, C.byref(done), C.byref(conv)),
+              name + "_cb")
+        if raised:
+            raise raised[0]
+    return done.value, (None if conv.value < 0 else conv.value)
 
 
 # ---- pairs above a threshold: libsimrank_select.so (include/simrank_select.h) on a plan's iterate, in place ----
@@ -159,7 +225,8 @@ class Selection:
     column blocks of this process's ranks) on ``ops``' stream.  Constructing it runs the COUNT pass and scans the counts
     (``total``: pairs in all blocks; nothing else crosses PCIe); ``emit()`` runs the EMIT pass and brings the hits back
     per block, rows in the solver's order; ``pairs()`` puts them into the caller's order.  ``timing``: HIP events around
-    each pass (``count_ms`` / ``emit_ms``, summed over the blocks)."""
+    each pass (``count_ms`` / ``emit_ms``, summed over the blocks).  The device blocks of a pass live in a
+    ``_driver.Scratch`` scope: the stream is synchronised before they go back to the pool, whatever ends the pass."""
 
     def __init__(self, ops, blocks, t, timing: bool = False):
         from . import _select
@@ -170,9 +237,9 @@ class Selection:
         self.count_ms = self.emit_ms = 0.0
         assert all(b["rows"] == n for b in blocks)
         self.offsets = []
-        cnt_dev = ops._malloc(4 * n)
         counts = np.empty(n, dtype=np.int32)
-        try:
+        with Scratch(ops) as scratch:
+            cnt_dev = scratch.malloc(4 * n)
             for b in blocks:
                 self._pass("count_ms", lambda: _select.check(self.sel.simrank_select_count(
                     b["ptr"], b["layout"], b["stride"], n, b["cols"], b["row_ids"], b["col_ids"], self.t32, cnt_dev,
@@ -187,8 +254,6 @@ class Selection:
             self.row_order = np.empty(n, dtype=np.int32)
             ops.d2h(self.row_order, blocks[0]["row_ids"])
             ops.synchronize()
-        finally:
-            ops._free(cnt_dev)
         self.total = sum(int(o[-1]) for o in self.offsets)
 
     def _pass(self, key, launch):
@@ -207,9 +272,9 @@ class Selection:
             ids = np.empty(tot, dtype=np.int32)
             vals = np.empty(tot, dtype=np.float32)
             if tot:
-                bufs = [ops._malloc(8 * (n + 1)), ops._malloc(4 * tot), ops._malloc(4 * tot)]
-                try:
-                    off_dev, ids_dev, val_dev = bufs
+                with Scratch(ops) as scratch:
+                    off_dev = scratch.malloc(8 * (n + 1))
+                    ids_dev, val_dev = scratch.malloc(4 * tot), scratch.malloc(4 * tot)
                     ops.h2d(off_dev, off)
                     self._pass("emit_ms", lambda: _select.check(self.sel.simrank_select_emit(
                         b["ptr"], b["layout"], b["stride"], n, b["cols"], b["row_ids"], b["col_ids"], self.t32, off_dev,
@@ -217,9 +282,6 @@ class Selection:
                     ops.d2h(ids, ids_dev)
                     ops.d2h(vals, val_dev)
                     ops.synchronize()
-                finally:
-                    for ptr in bufs:
-                        ops._free(ptr)
             pieces.append((off, ids, vals))
         return pieces
 
@@ -236,9 +298,122 @@ def _pairs_above(sel: Selection, max_pairs):
     return sel.pairs()
 
 
-class Plan:
+# ---- one similarity matrix of a plan object: the surface the solvers query (``side(j)`` of the four classes) ----
+class _Side:
+    """``n`` nodes, ``getters``: one ``get(key)`` per column block of the current iterate on this process's device.
+    ``result`` / ``topk`` (and ``rows`` / ``evidence_counts`` where the C ABI has them) come from the library behind
+    the side; the three below read the iterate in place through the companion libraries, before ``trim`` / ``free``."""
+
+    def selection(self, t, timing: bool = False) -> Selection:
+        """The count pass of ``pairs_above`` (``Selection``) over the column blocks."""
+        return Selection(self.ops, [_iterate_block(get) for get in self.getters], t, timing)
+
+    def reader(self):
+        """Node queries on the current iterate (``_query.Reader``)."""
+        return _query_reader(self.ops, self.getters)
+
+    def pairs_above(self, t, max_pairs=2 ** 27):
+        """(offsets int64 [n + 1], neighbour ids int32, values float32): row i (caller's order) lists the OTHER nodes c
+        with float64(S[i][c]) >= t, ascending — the masked ``np.nonzero`` of the dense result (several column blocks:
+        their hits concatenated per row, then sorted).  ValueError, with nothing transferred, when more than
+        ``max_pairs`` pairs qualify."""
+        return _pairs_above(self.selection(t), max_pairs)
+
+
+class _GpuSide(_Side):
+    """A side on one GPU: ``plan.handle`` behind simrank_plan_*, or with ``group`` = 1 | 2 behind simrank_biplan_*, whose
+    entry points take the group after the handle and are the same otherwise."""
+
+    def __init__(self, plan, n, group=None):
+        self.ops, self.plan, self.n = plan.ops, plan, n
+        self.stem, self.group = ("simrank_plan_", ()) if group is None else ("simrank_biplan_", (int(group),))
+
+    getters = property(lambda self: [self.get])       # (made when asked for: a side that held its own bound method would
+                                                      # be a cycle, and keep its plan's device memory until a collection)
+
+    def _call(self, entry, *args, what=None):
+        check(getattr(self.ops.lib, self.stem + entry)(self.plan.handle, *self.group, *args), what or self.stem + entry)
+
+    def get(self, key: str) -> int:
+        v = C.c_int64(0)
+        self._call("get", key.encode(), C.byref(v), what=f"{self.stem}get({key})")
+        return v.value
+
+    def result(self) -> np.ndarray:
+        out = hostpool.empty_f64(self.n, self.n)        # (a frame the caller dropped earlier, when there is one)
+        self._call("result_f64", out.ctypes.data, self.n)
+        return out
+
+    def rows(self, rows) -> np.ndarray:
+        """float32 [len(rows), n]: those rows of the current similarity matrix, caller's node order on both axes."""
+        ids = np.ascontiguousarray(rows, dtype=np.int32)
+        out = np.empty((ids.size, self.n), dtype=np.float32)
+        self._call("rows_f32", ids.ctypes.data, int(ids.size), out.ctypes.data, self.n)
+        return out
+
+    def topk(self, k: int, exclude_diag: bool = True):
+        """(ids int32 [n, k], values float32 [n, k]): the k most similar nodes of every node, caller's ids."""
+        idx = np.empty((self.n, k), dtype=np.int32)
+        val = np.empty((self.n, k), dtype=np.float32)
+        self._call("topk", int(k), int(exclude_diag), idx.ctypes.data, val.ctypes.data)
+        return idx, val
+
+    def evidence_counts(self) -> np.ndarray:
+        """uint8 [n, n] common in-neighbour counts (saturated at 255) that gate the side's update, caller's order."""
+        out = np.empty((self.n, self.n), dtype=np.uint8)
+        self._call("evidence_u8", out.ctypes.data, self.n)
+        return out
+
+
+def _shardplan_get(lib, handle, key: str) -> int:
+    """What a sharded plan (or a side of a sharded bipartite one) chose when it was created (simrank_shardplan_get)."""
+    v = C.c_int64(0)
+    check(lib.simrank_shardplan_get(handle, key.encode(), C.byref(v)), f"simrank_shardplan_get({key})")
+    return v.value
+
+
+class _ShardSide(_Side):
+    """A sharded side: ``arr``, the ``count`` simrank_shardplan* handles of this process's ranks — a ``ShardPlans``'
+    own, or what simrank_shardbiplan_side gives for a group (the C ABI makes a bipartite side a shardplan).  Collective
+    calls."""
+
+    def __init__(self, ops, arr, count, n):
+        self.ops, self.arr, self.count, self.n = ops, arr, count, n
+        self.handles = [C.c_void_p(h) for h in arr[:count]]
+        self.getters = [lambda k, h=h: _shardplan_get(ops.lib, h, k) for h in self.handles]
+
+    def info(self, i: int = 0) -> dict:
+        h = self.handles[i]
+        n, lo, hi = C.c_int64(), C.c_int64(), C.c_int64()
+        half, stages, updates = C.c_int32(), C.c_int32(), C.c_int32()
+        check(self.ops.lib.simrank_shardplan_info(h, C.byref(n), C.byref(lo), C.byref(hi), C.byref(half), C.byref(stages),
+                                                  C.byref(updates)), "simrank_shardplan_info")
+        return dict(n=n.value, col_lo=lo.value, col_hi=hi.value, half_form=bool(half.value), stages=stages.value,
+                    updates=updates.value, restrict_support=_shardplan_get(self.ops.lib, h, "restrict_support"))
+
+    def result(self, root: int = 0, i_am_root: bool = True):
+        """The whole matrix (float64, caller's order) on rank ``root``; None elsewhere."""
+        out = hostpool.empty_f64(self.n, self.n) if i_am_root else None
+        check(self.ops.lib.simrank_shardplan_result_f64(self.arr, self.count, int(root),
+                                                        out.ctypes.data if i_am_root else None, self.n),
+              "simrank_shardplan_result_f64")
+        return out
+
+    def topk(self, k: int, exclude_diag: bool = True, root: int = 0, i_am_root: bool = True):
+        """(ids int32 [n, k], values float32 [n, k]) on rank ``root``: the k most similar nodes of every node."""
+        idx = np.empty((self.n, k), dtype=np.int32) if i_am_root else None
+        val = np.empty((self.n, k), dtype=np.float32) if i_am_root else None
+        check(self.ops.lib.simrank_shardplan_topk(self.arr, self.count, int(root), int(k), int(exclude_diag),
+                                                  idx.ctypes.data if i_am_root else None,
+                                                  val.ctypes.data if i_am_root else None), "simrank_shardplan_topk")
+        return idx, val
+
+
+class Plan(_Owner):
     """The reference loop on one GPU behind the C ABI (simrank_plan_*: SimRank.py:124-141, :346-363,
     :440-455): CSR + per-row scale in the caller's node order in, S (float64, caller's order) out."""
+
+    _destroy = "simrank_plan_destroy"
 
     def __init__(self, ops, csr: CSR, rowscale=None, coef: float = 0.8, evidence: bool = False,
                  apriori=None, lbd: float = 0.0, reorder: bool = True, storage: str = "f32", dense_terms: int = 3):
@@ -246,34 +421,26 @@ class Plan:
         ``dense_terms``: 3 = exact products on the matrix cores, 1 = one fp16 operand term."""
         assert storage in ("f32", "fp16")
         self.ops = ops
-        rs = np.ascontiguousarray(csr.rowscale if rowscale is None else rowscale, dtype=np.float32)
-        rowptr = np.ascontiguousarray(csr.rowptr, dtype=np.int32)
-        col = np.ascontiguousarray(csr.col, dtype=np.int32)
-        ap = None if apriori is None else np.ascontiguousarray(apriori, dtype=np.float32)
-        opt = PlanOptions(coef=coef, lbd=lbd, apriori=None if ap is None else ap.ctypes.data,
-                          ld_apriori=0 if ap is None else ap.shape[1], evidence=int(evidence), reorder=int(reorder),
-                          storage_fp16=int(storage == "fp16"), dense_terms=int(dense_terms))
+        args, _keep = _csr_args(csr, csr.rowscale if rowscale is None else rowscale)
+        prior, _ap = _prior_fields(apriori)
+        opt = PlanOptions(coef=coef, lbd=lbd, evidence=int(evidence), reorder=int(reorder),
+                          storage_fp16=int(storage == "fp16"), dense_terms=int(dense_terms), **prior)
         h = C.c_void_p()
-        with HipOps._knob_lock:          # (the graph inside snapshots the process-wide knobs: not while another
-            check(ops.lib.simrank_plan_create(csr.n_rows, col.size, rowptr.ctypes.data,       # thread has per-graph ones set)
-                                              col.ctypes.data if col.size else None, rs.ctypes.data, C.byref(opt),
-                                              ops.stream, C.byref(h)), "simrank_plan_create")
+        # (the graph inside snapshots the process-wide knobs: not while another thread has per-graph ones set)
+        with HipOps._knob_lock:
+            check(ops.lib.simrank_plan_create(csr.n_rows, *args, C.byref(opt), ops.stream, C.byref(h)),
+                  "simrank_plan_create")
         self.handle, self.n = h, csr.n_rows
+
+    def side(self, j: int = 0) -> _GpuSide:
+        """The plan's one similarity matrix with the surface every plan class gives its sides (``_Side``)."""
+        assert j == 0
+        return _GpuSide(self, self.n)
 
     def run(self, iterations: int, eps: float, on_iteration=None, on_converged=None):
         """-> (updates applied, loop index at which the convergence test passed or None).  ``on_iteration(k)`` /
         ``on_converged(k)``: the reference's console hooks (SimRank.py:131-135), called from inside the C loop."""
-        done, conv = C.c_int32(0), C.c_int32(-1)
-        if on_iteration is None and on_converged is None:
-            check(self.ops.lib.simrank_plan_run(self.handle, int(iterations), float(eps), C.byref(done), C.byref(conv)),
-                  "simrank_plan_run")
-        else:
-            cb, raised = _progress_callback(on_iteration, on_converged)
-            check(self.ops.lib.simrank_plan_run_cb(self.handle, int(iterations), float(eps), cb, None, C.byref(done),
-                                                   C.byref(conv)), "simrank_plan_run_cb")
-            if raised:
-                raise raised[0]
-        return done.value, (None if conv.value < 0 else conv.value)
+        return _run(self.ops.lib, "simrank_plan_run", (self.handle,), iterations, eps, on_iteration, on_converged)
 
     def set_timing(self, updates: int):
         """HIP events around both legs of the next ``updates`` updates, on the plan's stream (0 = off)."""
@@ -291,18 +458,6 @@ class Plan:
         check(self.ops.lib.simrank_plan_info(self.handle, None, None, C.byref(g)), "simrank_plan_info")
         return g
 
-    def get(self, key: str) -> int:
-        """What the plan chose when it was created (simrank_plan_get): "restrict_support"."""
-        v = C.c_int64(0)
-        check(self.ops.lib.simrank_plan_get(self.handle, key.encode(), C.byref(v)), f"simrank_plan_get({key})")
-        return v.value
-
-    def evidence_counts(self) -> np.ndarray:
-        """uint8 [n, n] common in-neighbour counts (saturated at 255) in the caller's order."""
-        out = np.empty((self.n, self.n), dtype=np.uint8)
-        check(self.ops.lib.simrank_plan_evidence_u8(self.handle, out.ctypes.data, self.n), "simrank_plan_evidence_u8")
-        return out
-
     def trim(self):
         """Release the matrices of the loop; the evidence counts stay readable."""
         if self.handle:
@@ -316,87 +471,110 @@ class Plan:
         check(self.ops.lib.simrank_plan_step(self.handle, float(eps), int(exact_count), C.byref(c)), "simrank_plan_step")
         return c.value
 
+    # the side's surface under the names the plan has always had (``get``: what the plan chose when it was created,
+    # "restrict_support", and where its iterate is)
+    def get(self, key: str) -> int:
+        return self.side().get(key)
+
+    def evidence_counts(self) -> np.ndarray:
+        return self.side().evidence_counts()
+
     def result(self) -> np.ndarray:
-        out = hostpool.empty_f64(self.n, self.n)        # (a frame the caller dropped earlier, when there is one)
-        check(self.ops.lib.simrank_plan_result_f64(self.handle, out.ctypes.data, self.n), "simrank_plan_result_f64")
-        return out
+        return self.side().result()
 
     def rows(self, rows) -> np.ndarray:
-        """float32 [len(rows), n]: those rows of the current similarity matrix, caller's node order on both axes."""
-        ids = np.ascontiguousarray(rows, dtype=np.int32)
-        out = np.empty((ids.size, self.n), dtype=np.float32)
-        check(self.ops.lib.simrank_plan_rows_f32(self.handle, ids.ctypes.data, int(ids.size), out.ctypes.data, self.n),
-              "simrank_plan_rows_f32")
-        return out
+        return self.side().rows(rows)
 
     def topk(self, k: int, exclude_diag: bool = True):
-        """(ids int32 [n, k], values float32 [n, k]): the k most similar nodes of every node, caller's ids."""
-        idx = np.empty((self.n, k), dtype=np.int32)
-        val = np.empty((self.n, k), dtype=np.float32)
-        check(self.ops.lib.simrank_plan_topk(self.handle, int(k), int(exclude_diag), idx.ctypes.data, val.ctypes.data),
-              "simrank_plan_topk")
-        return idx, val
+        return self.side().topk(k, exclude_diag)
 
     def selection(self, t, timing: bool = False) -> Selection:
-        """The count pass of ``pairs_above`` (``Selection``): the current iterate, read in place."""
-        return Selection(self.ops, [_iterate_block(self.get)], t, timing)
+        return self.side().selection(t, timing)
 
     def reader(self):
-        """Node queries on the current iterate, read in place (``_query.Reader``).  Before ``trim``."""
-        return _query_reader(self.ops, [self.get])
+        return self.side().reader()
 
     def pairs_above(self, t, max_pairs=2 ** 27):
-        """(offsets int64 [n + 1], neighbour ids int32, values float32): row i (caller's order) lists the OTHER nodes c
-        with float64(S[i][c]) >= t, ascending — the masked ``np.nonzero`` of the dense result.  ValueError, with nothing
-        transferred, when more than ``max_pairs`` pairs qualify.  Before ``trim``."""
-        return _pairs_above(self.selection(t), max_pairs)
+        return self.side().pairs_above(t, max_pairs)
 
-    def free(self):
+
+class BiPlan(_Owner):
+    """The bipartite loop on one GPU behind the C ABI (simrank_biplan_*: SimRank.py:288-302, :410-424,
+    :478-492): the group-1 CSR (columns = group-2 ids) and both groups' row scales in, (S1, S2) out."""
+
+    _destroy = "simrank_biplan_destroy"
+
+    def __init__(self, ops, csr12: CSR, rowscale1, rowscale2, c1: float = 0.8, c2: float = 0.8,
+                 evidence: bool = False, apriori1=None, apriori2=None, lbd1: float = 0.0, lbd2: float = 0.0,
+                 reorder: bool = True, strict_reference: bool = False):
+        self.ops = ops
+        assert np.size(rowscale1) == csr12.n_rows and np.size(rowscale2) == csr12.n_cols
+        args, _keep = _csr_args(csr12, rowscale1, rowscale2)
+        opt, _priors = _biplan_options(c1, c2, lbd1, lbd2, apriori1, apriori2, evidence, reorder, strict_reference)
+        h = C.c_void_p()
+        with HipOps._knob_lock:
+            check(ops.lib.simrank_biplan_create(csr12.n_rows, csr12.n_cols, *args, C.byref(opt), ops.stream, C.byref(h)),
+                  "simrank_biplan_create")
+        self.handle, self.n1, self.n2 = h, csr12.n_rows, csr12.n_cols
+
+    def side(self, j: int) -> _GpuSide:
+        """Group j + 1's similarity matrix (``_Side``)."""
+        return _GpuSide(self, self.n1 if j == 0 else self.n2, j + 1)       # (another j: the library refuses the group)
+
+    def run(self, iterations: int, eps: float, on_iteration=None, on_converged=None):
+        """-> (loop bodies applied, loop index at which the convergence test passed or None); hooks as ``Plan.run``."""
+        return _run(self.ops.lib, "simrank_biplan_run", (self.handle,), iterations, eps, on_iteration, on_converged)
+
+    def trim(self):
         if self.handle:
-            self.ops.lib.simrank_plan_destroy(self.handle)
-            self.handle = None
+            check(self.ops.lib.simrank_biplan_trim(self.handle), "simrank_biplan_trim")
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def reset(self):
+        check(self.ops.lib.simrank_biplan_reset(self.handle), "simrank_biplan_reset")
+
+    def step(self, eps: float, exact_count: bool = True):
+        c1, c2 = C.c_int64(0), C.c_int64(0)
+        check(self.ops.lib.simrank_biplan_step(self.handle, float(eps), int(exact_count), C.byref(c1), C.byref(c2)),
+              "simrank_biplan_step")
+        return c1.value, c2.value
+
+    def result(self):
+        return self.result_group(1), self.result_group(2)
+
+    # group 1 | 2's side under the names the plan has always had
+    def result_group(self, group: int) -> np.ndarray:
+        return self.side(group - 1).result()
+
+    def rows(self, group: int, rows) -> np.ndarray:
+        return self.side(group - 1).rows(rows)
+
+    def topk(self, group: int, k: int, exclude_diag: bool = True):
+        return self.side(group - 1).topk(k, exclude_diag)
+
+    def get(self, group: int, key: str) -> int:
+        return self.side(group - 1).get(key)
+
+    def evidence_counts(self, group: int) -> np.ndarray:
+        return self.side(group - 1).evidence_counts()
+
+    def selection(self, group: int, t, timing: bool = False) -> Selection:
+        return self.side(group - 1).selection(t, timing)
+
+    def reader(self, group: int):
+        return self.side(group - 1).reader()
+
+    def pairs_above(self, group: int, t, max_pairs=2 ** 27):
+        return self.side(group - 1).pairs_above(t, max_pairs)
 
 
-class ShardPlanOptions(C.Structure):           # struct simrank_shardplan_options
-    _fields_ = [("coef", C.c_float), ("lbd", C.c_float), ("apriori", C.c_void_p), ("ld_apriori", C.c_int64),
-                ("evidence", C.c_int32), ("reorder", C.c_int32), ("leg2_form", C.c_int32), ("stages", C.c_int32),
-                ("wire_fp16", C.c_int32), ("storage_fp16", C.c_int32)]
+class _ShardGroup(_Owner):
+    """What the two sharded classes share: the communicators of this process's ranks — an in-process group of ``world``
+    virtual ranks that the object owns, or the one it was given —, one handle per communicator, and their tear-down."""
 
-
-def _shardplan_get(lib, handle, key: str) -> int:
-    """What a sharded plan (or a side of a sharded bipartite one) chose when it was created (simrank_shardplan_get)."""
-    v = C.c_int64(0)
-    check(lib.simrank_shardplan_get(handle, key.encode(), C.byref(v)), f"simrank_shardplan_get({key})")
-    return v.value
-
-
-class ShardPlans:
-    """This process's share of a SHARDED fit behind the C ABI (simrank_shardplan_*: K10, S split by column block over
-    ``world`` ranks): ONE plan when ``comm`` is an RCCL communicator of a multi-process world (``rccl_comm``), or all
-    ``world`` plans of an in-process group of virtual ranks on this device (``comm=None``: the exchanges are device
-    copies — tests and single-GPU emulation).  ``run`` / ``step`` / ``result`` are collective."""
-
-    def __init__(self, ops, csr: CSR, rowscale=None, world: int = 1, comm=None, coef: float = 0.8, evidence: bool = False,
-                 apriori=None, lbd: float = 0.0, reorder: bool = True, leg2_form: int = -1, stages: int = 0,
-                 wire_fp16: bool = False, storage: str = "f32"):
-        """``storage="fp16"``: matrices held in fp16 on every rank (config 5's reduced precision on shards)."""
-        assert storage in ("f32", "fp16")
-        self.ops, self.n = ops, csr.n_rows
-        lib = ops.lib
-        rs = np.ascontiguousarray(csr.rowscale if rowscale is None else rowscale, dtype=np.float32)
-        rowptr = np.ascontiguousarray(csr.rowptr, dtype=np.int32)
-        col = np.ascontiguousarray(csr.col, dtype=np.int32)
-        ap = None if apriori is None else np.ascontiguousarray(apriori, dtype=np.float32)
-        opt = ShardPlanOptions(coef=coef, lbd=lbd, apriori=None if ap is None else ap.ctypes.data,
-                               ld_apriori=0 if ap is None else ap.shape[1], evidence=int(evidence), reorder=int(reorder),
-                               leg2_form=int(leg2_form), stages=int(stages), wire_fp16=int(wire_fp16),
-                               storage_fp16=int(storage == "fp16"))
+    def _create(self, world, comm, create):
+        """``create(comm, &handle)`` per communicator, under the knob lock -> the handles, also as the array
+        (``_arr``) the collective entry points take."""
+        lib = self.ops.lib
         self.own_comms = comm is None
         if comm is None:
             arr = (C.c_void_p * world)()
@@ -404,15 +582,46 @@ class ShardPlans:
             self.comms = [C.c_void_p(arr[r]) for r in range(world)]
         else:
             self.comms = [comm]
-        self.plans = []
+        self._handles = []
         with HipOps._knob_lock:
             for c in self.comms:
                 h = C.c_void_p()
-                check(lib.simrank_shardplan_create(csr.n_rows, col.size, rowptr.ctypes.data,
-                                                   col.ctypes.data if col.size else None, rs.ctypes.data, C.byref(opt),
-                                                   c, ops.stream, C.byref(h)), "simrank_shardplan_create")
-                self.plans.append(h)
-        self._arr = (C.c_void_p * len(self.plans))(*[h.value for h in self.plans])
+                create(c, h)
+                self._handles.append(h)
+        self._arr = (C.c_void_p * len(self._handles))(*[h.value for h in self._handles])
+
+    def free(self):
+        """Destroy the handles, then the communicators if they are this object's own."""
+        lib = self.ops.lib
+        while self._handles:
+            getattr(lib, self._destroy)(self._handles.pop(0))
+        if self.own_comms:
+            for c in self.comms:
+                lib.simrank_comm_destroy(c)
+        self.comms = []
+
+
+class ShardPlans(_ShardGroup):
+    """This process's share of a SHARDED fit behind the C ABI (simrank_shardplan_*: K10, S split by column block over
+    ``world`` ranks): ONE plan when ``comm`` is an RCCL communicator of a multi-process world (``rccl_comm``), or all
+    ``world`` plans of an in-process group of virtual ranks on this device (``comm=None``: the exchanges are device
+    copies — tests and single-GPU emulation).  ``run`` / ``step`` / ``result`` are collective."""
+
+    _destroy = "simrank_shardplan_destroy"
+    plans = property(lambda self: self._handles)      # the handles under their public name (``free`` empties the list)
+
+    def __init__(self, ops, csr: CSR, rowscale=None, world: int = 1, comm=None, coef: float = 0.8, evidence: bool = False,
+                 apriori=None, lbd: float = 0.0, reorder: bool = True, leg2_form: int = -1, stages: int = 0,
+                 wire_fp16: bool = False, storage: str = "f32"):
+        """``storage="fp16"``: matrices held in fp16 on every rank (config 5's reduced precision on shards)."""
+        assert storage in ("f32", "fp16")
+        self.ops, self.n = ops, csr.n_rows
+        args, _keep = _csr_args(csr, csr.rowscale if rowscale is None else rowscale)
+        prior, _ap = _prior_fields(apriori)
+        opt = ShardPlanOptions(coef=coef, lbd=lbd, evidence=int(evidence), reorder=int(reorder), leg2_form=int(leg2_form),
+                               stages=int(stages), wire_fp16=int(wire_fp16), storage_fp16=int(storage == "fp16"), **prior)
+        self._create(world, comm, lambda c, h: check(ops.lib.simrank_shardplan_create(
+            csr.n_rows, *args, C.byref(opt), c, ops.stream, C.byref(h)), "simrank_shardplan_create"))
 
     @staticmethod
     def rccl_unique_id(lib) -> bytes:
@@ -426,13 +635,14 @@ class ShardPlans:
         check(lib.simrank_comm_create(C.c_char_p(unique_id), int(rank), int(world), C.byref(h)), "simrank_comm_create")
         return h
 
+    def side(self, j: int = 0) -> _ShardSide:
+        """The column blocks of this process's plans (every rank of an in-process group: the whole matrix; this rank's
+        block in an RCCL world) with the surface every plan class gives its sides (``_Side``)."""
+        assert j == 0
+        return _ShardSide(self.ops, self._arr, len(self._handles), self.n)
+
     def info(self, i: int = 0) -> dict:
-        n, lo, hi = C.c_int64(), C.c_int64(), C.c_int64()
-        half, stages, updates = C.c_int32(), C.c_int32(), C.c_int32()
-        check(self.ops.lib.simrank_shardplan_info(self.plans[i], C.byref(n), C.byref(lo), C.byref(hi), C.byref(half),
-                                                  C.byref(stages), C.byref(updates)), "simrank_shardplan_info")
-        return dict(n=n.value, col_lo=lo.value, col_hi=hi.value, half_form=bool(half.value), stages=stages.value,
-                    updates=updates.value, restrict_support=_shardplan_get(self.ops.lib, self.plans[i], "restrict_support"))
+        return self.side().info(i)
 
     TIMING_KEYS = ("leg1_ms", "exchange1_ms", "wait_before_leg2_ms", "leg2_ms", "count_and_exchange2_ms", "update_ms")
 
@@ -450,20 +660,17 @@ class ShardPlans:
         return out
 
     def reset(self):
-        check(self.ops.lib.simrank_shardplan_reset(self._arr, len(self.plans)), "simrank_shardplan_reset")
+        check(self.ops.lib.simrank_shardplan_reset(self._arr, len(self._handles)), "simrank_shardplan_reset")
 
     def step(self, eps: float, exact_count: bool = True) -> int:
         c = C.c_int64(0)
-        check(self.ops.lib.simrank_shardplan_step(self._arr, len(self.plans), float(eps), int(exact_count), C.byref(c)),
+        check(self.ops.lib.simrank_shardplan_step(self._arr, len(self._handles), float(eps), int(exact_count), C.byref(c)),
               "simrank_shardplan_step")
         return c.value
 
     def run(self, iterations: int, eps: float):
         """-> (updates applied, loop index at which the convergence test passed or None); the same on every rank."""
-        done, conv = C.c_int32(0), C.c_int32(-1)
-        check(self.ops.lib.simrank_shardplan_run(self._arr, len(self.plans), int(iterations), float(eps), C.byref(done),
-                                                 C.byref(conv)), "simrank_shardplan_run")
-        return done.value, (None if conv.value < 0 else conv.value)
+        return _run(self.ops.lib, "simrank_shardplan_run", (self._arr, len(self._handles)), iterations, eps)
 
     def block(self, i: int = 0):
         """(float64 [n, columns of plan i] in the caller's row order, the caller's node ids of those columns)."""
@@ -475,56 +682,21 @@ class ShardPlans:
         check(self.ops.lib.simrank_shardplan_columns(self.plans[i], ids.ctypes.data), "simrank_shardplan_columns")
         return out, ids
 
+    # the side's surface under the names the class has always had (collective where the side's are)
     def result(self, root: int = 0, i_am_root: bool = True):
-        """The whole matrix (float64, caller's order) on rank ``root``; None elsewhere.  Collective."""
-        out = hostpool.empty_f64(self.n, self.n) if i_am_root else None
-        check(self.ops.lib.simrank_shardplan_result_f64(self._arr, len(self.plans), int(root),
-                                                        out.ctypes.data if out is not None else None, self.n),
-              "simrank_shardplan_result_f64")
-        return out
+        return self.side().result(root, i_am_root)
 
     def topk(self, k: int, exclude_diag: bool = True, root: int = 0, i_am_root: bool = True):
-        """(ids int32 [n, k], values float32 [n, k]) on rank ``root``: the k most similar nodes of every node.  Collective."""
-        idx = np.empty((self.n, k), dtype=np.int32) if i_am_root else None
-        val = np.empty((self.n, k), dtype=np.float32) if i_am_root else None
-        check(self.ops.lib.simrank_shardplan_topk(self._arr, len(self.plans), int(root), int(k), int(exclude_diag),
-                                                  idx.ctypes.data if i_am_root else None,
-                                                  val.ctypes.data if i_am_root else None), "simrank_shardplan_topk")
-        return idx, val
+        return self.side().topk(k, exclude_diag, root, i_am_root)
 
     def selection(self, t, timing: bool = False) -> Selection:
-        """The count pass over the column blocks of this process's plans (every rank of an in-process group; this rank's
-        block in an RCCL world)."""
-        lib = self.ops.lib
-        return Selection(self.ops, [_iterate_block(lambda k, h=h: _shardplan_get(lib, h, k)) for h in self.plans], t,
-                         timing)
+        return self.side().selection(t, timing)
 
     def reader(self):
-        """Node queries over the column blocks of this process's plans (``_query.Reader``)."""
-        lib = self.ops.lib
-        return _query_reader(self.ops, [lambda k, h=h: _shardplan_get(lib, h, k) for h in self.plans])
+        return self.side().reader()
 
     def pairs_above(self, t, max_pairs=2 ** 27):
-        """As ``Plan.pairs_above``, over the column blocks of this process's plans (the whole matrix in an in-process
-        group): the blocks' hits concatenated per row, then sorted."""
-        return _pairs_above(self.selection(t), max_pairs)
-
-    def free(self):
-        lib = self.ops.lib
-        for h in self.plans:
-            lib.simrank_shardplan_destroy(h)
-        self.plans = []
-        if self.own_comms:
-            for c in self.comms:
-                lib.simrank_comm_destroy(c)
-        self.comms = []
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
+        return self.side().pairs_above(t, max_pairs)
 
 
 class ThreadRanks:
@@ -569,10 +741,14 @@ class ThreadRanks:
             self.lib.simrank_comm_destroy(c)
         self.comms = []
 
-class ShardBiPlans:
+
+class ShardBiPlans(_ShardGroup):
     """This process's share of a SHARDED two-matrix fit behind the C ABI (simrank_shardbiplan_*: the loops of
     SimRank.py:288-302, :410-424, :478-492 with S1 and S2 split by column block over ``world`` ranks): one pair of plans
     over an RCCL communicator, or all ``world`` pairs of an in-process group (``comm=None``).  Collective calls."""
+
+    _destroy = "simrank_shardbiplan_destroy"
+    pairs = property(lambda self: self._handles)      # the handles under their public name (``free`` empties the list)
 
     def __init__(self, ops, csr12: CSR, rowscale1, rowscale2, world: int = 1, comm=None, c1: float = 0.8, c2: float = 0.8,
                  evidence: bool = False, apriori1=None, apriori2=None, lbd1: float = 0.0, lbd2: float = 0.0,
@@ -580,238 +756,55 @@ class ShardBiPlans:
                  wire_fp16: bool = False):
         self.ops, self.n1, self.n2 = ops, csr12.n_rows, csr12.n_cols
         lib = ops.lib
-        rowptr = np.ascontiguousarray(csr12.rowptr, dtype=np.int32)
-        col = np.ascontiguousarray(csr12.col, dtype=np.int32)
-        rs1 = np.ascontiguousarray(rowscale1, dtype=np.float32)
-        rs2 = np.ascontiguousarray(rowscale2, dtype=np.float32)
-        a1 = None if apriori1 is None else np.ascontiguousarray(apriori1, dtype=np.float32)
-        a2 = None if apriori2 is None else np.ascontiguousarray(apriori2, dtype=np.float32)
-        opt = BiPlanOptions(c1=c1, c2=c2, lbd1=lbd1, lbd2=lbd2,
-                            apriori1=None if a1 is None else a1.ctypes.data, ld_apriori1=0 if a1 is None else a1.shape[1],
-                            apriori2=None if a2 is None else a2.ctypes.data, ld_apriori2=0 if a2 is None else a2.shape[1],
-                            evidence=int(evidence), reorder=int(reorder), strict_reference=int(strict_reference))
-        self.own_comms = comm is None
-        if comm is None:
-            arr = (C.c_void_p * world)()
-            check(lib.simrank_comm_local_group(int(world), arr), "simrank_comm_local_group")
-            self.comms = [C.c_void_p(arr[r]) for r in range(world)]
-        else:
-            self.comms = [comm]
-        self.pairs = []
-        with HipOps._knob_lock:
-            for c in self.comms:
-                h = C.c_void_p()
-                check(lib.simrank_shardbiplan_create(csr12.n_rows, csr12.n_cols, col.size, rowptr.ctypes.data,
-                                                     col.ctypes.data if col.size else None, rs1.ctypes.data, rs2.ctypes.data,
-                                                     C.byref(opt), int(leg2_form), int(stages), int(wire_fp16), c, ops.stream,
-                                                     C.byref(h)), "simrank_shardbiplan_create")
-                self.pairs.append(h)
-        self._arr = (C.c_void_p * len(self.pairs))(*[h.value for h in self.pairs])
-        self._sides = {}
+        args, _keep = _csr_args(csr12, rowscale1, rowscale2)
+        opt, _priors = _biplan_options(c1, c2, lbd1, lbd2, apriori1, apriori2, evidence, reorder, strict_reference)
+        self._create(world, comm, lambda c, h: check(lib.simrank_shardbiplan_create(
+            csr12.n_rows, csr12.n_cols, *args, C.byref(opt), int(leg2_form), int(stages), int(wire_fp16), c, ops.stream,
+            C.byref(h)), "simrank_shardbiplan_create"))
+        self._sides = {}                 # group -> the simrank_shardplan* handles of its side, one per local pair
         for group in (1, 2):
             hs = []
             for h in self.pairs:
                 sp = C.c_void_p()
                 check(lib.simrank_shardbiplan_side(h, group, C.byref(sp)), "simrank_shardbiplan_side")
-                hs.append(sp)
-            self._sides[group] = (C.c_void_p * len(hs))(*[x.value for x in hs])
+                hs.append(sp.value)
+            self._sides[group] = (C.c_void_p * len(hs))(*hs)
+
+    def side(self, j: int) -> _ShardSide:
+        """Group j + 1's column blocks on this process's ranks (``_Side``)."""
+        return _ShardSide(self.ops, self._sides[j + 1], len(self._handles), self.n1 if j == 0 else self.n2)
 
     def reset(self):
-        check(self.ops.lib.simrank_shardbiplan_reset(self._arr, len(self.pairs)), "simrank_shardbiplan_reset")
+        check(self.ops.lib.simrank_shardbiplan_reset(self._arr, len(self._handles)), "simrank_shardbiplan_reset")
 
     def step(self, eps: float, exact_count: bool = True):
         c1, c2 = C.c_int64(0), C.c_int64(0)
-        check(self.ops.lib.simrank_shardbiplan_step(self._arr, len(self.pairs), float(eps), int(exact_count), C.byref(c1),
+        check(self.ops.lib.simrank_shardbiplan_step(self._arr, len(self._handles), float(eps), int(exact_count), C.byref(c1),
                                                     C.byref(c2)), "simrank_shardbiplan_step")
         return c1.value, c2.value
 
     def run(self, iterations: int, eps: float):
         """-> (loop bodies applied, loop index at which the convergence test passed or None); the same on every rank."""
-        done, conv = C.c_int32(0), C.c_int32(-1)
-        check(self.ops.lib.simrank_shardbiplan_run(self._arr, len(self.pairs), int(iterations), float(eps), C.byref(done),
-                                                   C.byref(conv)), "simrank_shardbiplan_run")
-        return done.value, (None if conv.value < 0 else conv.value)
+        return _run(self.ops.lib, "simrank_shardbiplan_run", (self._arr, len(self._handles)), iterations, eps)
 
+    # group 1 | 2's side under the names the class has always had
     def side_info(self, group: int, i: int = 0) -> dict:
-        n, lo, hi = C.c_int64(), C.c_int64(), C.c_int64()
-        half, stages, updates = C.c_int32(), C.c_int32(), C.c_int32()
-        check(self.ops.lib.simrank_shardplan_info(C.c_void_p(self._sides[group][i]), C.byref(n), C.byref(lo), C.byref(hi),
-                                                  C.byref(half), C.byref(stages), C.byref(updates)), "simrank_shardplan_info")
-        return dict(n=n.value, col_lo=lo.value, col_hi=hi.value, half_form=bool(half.value), stages=stages.value,
-                    updates=updates.value,
-                    restrict_support=_shardplan_get(self.ops.lib, C.c_void_p(self._sides[group][i]), "restrict_support"))
+        return self.side(group - 1).info(i)
 
     def result(self, group: int, root: int = 0, i_am_root: bool = True):
-        """Group 1 | 2's whole matrix (float64, caller's order) on rank ``root``; None elsewhere.  Collective."""
-        n = self.n1 if group == 1 else self.n2
-        out = hostpool.empty_f64(n, n) if i_am_root else None
-        check(self.ops.lib.simrank_shardplan_result_f64(self._sides[group], len(self.pairs), int(root),
-                                                        out.ctypes.data if out is not None else None, n),
-              "simrank_shardplan_result_f64")
-        return out
+        return self.side(group - 1).result(root, i_am_root)
 
     def topk(self, group: int, k: int, exclude_diag: bool = True, root: int = 0, i_am_root: bool = True):
-        n = self.n1 if group == 1 else self.n2
-        idx = np.empty((n, k), dtype=np.int32) if i_am_root else None
-        val = np.empty((n, k), dtype=np.float32) if i_am_root else None
-        check(self.ops.lib.simrank_shardplan_topk(self._sides[group], len(self.pairs), int(root), int(k), int(exclude_diag),
-                                                  idx.ctypes.data if i_am_root else None,
-                                                  val.ctypes.data if i_am_root else None), "simrank_shardplan_topk")
-        return idx, val
+        return self.side(group - 1).topk(k, exclude_diag, root, i_am_root)
 
     def selection(self, group: int, t, timing: bool = False) -> Selection:
-        lib = self.ops.lib
-        return Selection(self.ops, [_iterate_block(lambda k, h=h: _shardplan_get(lib, C.c_void_p(h), k))
-                                    for h in self._sides[group]], t, timing)
+        return self.side(group - 1).selection(t, timing)
 
     def reader(self, group: int):
-        """Node queries on group 1 | 2's column blocks (``_query.Reader``)."""
-        lib = self.ops.lib
-        return _query_reader(self.ops, [lambda k, h=h: _shardplan_get(lib, C.c_void_p(h), k) for h in self._sides[group]])
+        return self.side(group - 1).reader()
 
     def pairs_above(self, group: int, t, max_pairs=2 ** 27):
-        """As ``ShardPlans.pairs_above``, for group 1 | 2."""
-        return _pairs_above(self.selection(group, t), max_pairs)
-
-    def free(self):
-        lib = self.ops.lib
-        for h in self.pairs:
-            lib.simrank_shardbiplan_destroy(h)
-        self.pairs = []
-        if self.own_comms:
-            for c in self.comms:
-                lib.simrank_comm_destroy(c)
-        self.comms = []
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class BiPlanOptions(C.Structure):              # struct simrank_biplan_options
-    _fields_ = [("c1", C.c_float), ("c2", C.c_float), ("lbd1", C.c_float), ("lbd2", C.c_float),
-                ("apriori1", C.c_void_p), ("ld_apriori1", C.c_int64), ("apriori2", C.c_void_p),
-                ("ld_apriori2", C.c_int64), ("evidence", C.c_int32), ("reorder", C.c_int32),
-                ("strict_reference", C.c_int32)]
-
-
-class BiPlan:
-    """The bipartite loop on one GPU behind the C ABI (simrank_biplan_*: SimRank.py:288-302, :410-424,
-    :478-492): the group-1 CSR (columns = group-2 ids) and both groups' row scales in, (S1, S2) out."""
-
-    def __init__(self, ops, csr12: CSR, rowscale1, rowscale2, c1: float = 0.8, c2: float = 0.8,
-                 evidence: bool = False, apriori1=None, apriori2=None, lbd1: float = 0.0, lbd2: float = 0.0,
-                 reorder: bool = True, strict_reference: bool = False):
-        self.ops = ops
-        rowptr = np.ascontiguousarray(csr12.rowptr, dtype=np.int32)
-        col = np.ascontiguousarray(csr12.col, dtype=np.int32)
-        rs1 = np.ascontiguousarray(rowscale1, dtype=np.float32)
-        rs2 = np.ascontiguousarray(rowscale2, dtype=np.float32)
-        assert rs1.size == csr12.n_rows and rs2.size == csr12.n_cols
-        a1 = None if apriori1 is None else np.ascontiguousarray(apriori1, dtype=np.float32)
-        a2 = None if apriori2 is None else np.ascontiguousarray(apriori2, dtype=np.float32)
-        opt = BiPlanOptions(c1=c1, c2=c2, lbd1=lbd1, lbd2=lbd2,
-                            apriori1=None if a1 is None else a1.ctypes.data, ld_apriori1=0 if a1 is None else a1.shape[1],
-                            apriori2=None if a2 is None else a2.ctypes.data, ld_apriori2=0 if a2 is None else a2.shape[1],
-                            evidence=int(evidence), reorder=int(reorder), strict_reference=int(strict_reference))
-        h = C.c_void_p()
-        with HipOps._knob_lock:
-            check(ops.lib.simrank_biplan_create(csr12.n_rows, csr12.n_cols, col.size, rowptr.ctypes.data,
-                                                col.ctypes.data if col.size else None, rs1.ctypes.data, rs2.ctypes.data,
-                                                C.byref(opt), ops.stream, C.byref(h)), "simrank_biplan_create")
-        self.handle, self.n1, self.n2 = h, csr12.n_rows, csr12.n_cols
-
-    def run(self, iterations: int, eps: float, on_iteration=None, on_converged=None):
-        """-> (loop bodies applied, loop index at which the convergence test passed or None); hooks as ``Plan.run``."""
-        done, conv = C.c_int32(0), C.c_int32(-1)
-        if on_iteration is None and on_converged is None:
-            check(self.ops.lib.simrank_biplan_run(self.handle, int(iterations), float(eps), C.byref(done), C.byref(conv)),
-                  "simrank_biplan_run")
-        else:
-            cb, raised = _progress_callback(on_iteration, on_converged)
-            check(self.ops.lib.simrank_biplan_run_cb(self.handle, int(iterations), float(eps), cb, None, C.byref(done),
-                                                     C.byref(conv)), "simrank_biplan_run_cb")
-            if raised:
-                raise raised[0]
-        return done.value, (None if conv.value < 0 else conv.value)
-
-    def result_group(self, group: int) -> np.ndarray:
-        n = self.n1 if group == 1 else self.n2
-        m = hostpool.empty_f64(n, n)
-        check(self.ops.lib.simrank_biplan_result_f64(self.handle, group, m.ctypes.data, n), "simrank_biplan_result_f64")
-        return m
-
-    def rows(self, group: int, rows) -> np.ndarray:
-        """float32 [len(rows), n_group]: those rows of group 1 | 2's current similarity matrix, caller's order on both axes."""
-        n = self.n1 if group == 1 else self.n2
-        ids = np.ascontiguousarray(rows, dtype=np.int32)
-        out = np.empty((ids.size, n), dtype=np.float32)
-        check(self.ops.lib.simrank_biplan_rows_f32(self.handle, int(group), ids.ctypes.data, int(ids.size), out.ctypes.data, n),
-              "simrank_biplan_rows_f32")
-        return out
-
-    def topk(self, group: int, k: int, exclude_diag: bool = True):
-        """(ids int32 [n, k], values float32 [n, k]) of group 1 | 2, caller's ids."""
-        n = self.n1 if group == 1 else self.n2
-        idx = np.empty((n, k), dtype=np.int32)
-        val = np.empty((n, k), dtype=np.float32)
-        check(self.ops.lib.simrank_biplan_topk(self.handle, int(group), int(k), int(exclude_diag), idx.ctypes.data,
-                                               val.ctypes.data), "simrank_biplan_topk")
-        return idx, val
-
-    def get(self, group: int, key: str) -> int:
-        """What group 1 | 2's side chose when the plan was created (simrank_biplan_get): "restrict_support"."""
-        v = C.c_int64(0)
-        check(self.ops.lib.simrank_biplan_get(self.handle, int(group), key.encode(), C.byref(v)), f"simrank_biplan_get({key})")
-        return v.value
-
-    def selection(self, group: int, t, timing: bool = False) -> Selection:
-        return Selection(self.ops, [_iterate_block(lambda k: self.get(group, k))], t, timing)
-
-    def reader(self, group: int):
-        """Node queries on group 1 | 2's current iterate (``_query.Reader``).  Before ``trim``."""
-        return _query_reader(self.ops, [lambda k: self.get(group, k)])
-
-    def pairs_above(self, group: int, t, max_pairs=2 ** 27):
-        """As ``Plan.pairs_above``, for group 1 | 2."""
-        return _pairs_above(self.selection(group, t), max_pairs)
-
-    def evidence_counts(self, group: int) -> np.ndarray:
-        """uint8 [n, n] counts gating group 1 | 2's update, caller's order."""
-        n = self.n1 if group == 1 else self.n2
-        out = np.empty((n, n), dtype=np.uint8)
-        check(self.ops.lib.simrank_biplan_evidence_u8(self.handle, int(group), out.ctypes.data, n),
-              "simrank_biplan_evidence_u8")
-        return out
-
-    def trim(self):
-        if self.handle:
-            check(self.ops.lib.simrank_biplan_trim(self.handle), "simrank_biplan_trim")
-
-    def reset(self):
-        check(self.ops.lib.simrank_biplan_reset(self.handle), "simrank_biplan_reset")
-
-    def step(self, eps: float, exact_count: bool = True):
-        c1, c2 = C.c_int64(0), C.c_int64(0)
-        check(self.ops.lib.simrank_biplan_step(self.handle, float(eps), int(exact_count), C.byref(c1), C.byref(c2)),
-              "simrank_biplan_step")
-        return c1.value, c2.value
-
-    def result(self):
-        return self.result_group(1), self.result_group(2)
-
-    def free(self):
-        if self.handle:
-            self.ops.lib.simrank_biplan_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        return self.side(group - 1).pairs_above(t, max_pairs)
 
 
 # rows appended to every panel of a panel-blocked matrix (panels are then not a power of two apart); a measurement knob

@@ -13,8 +13,9 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
     mode              "auto" | "sparse": the gather legs ("dense" | "hybrid", BASELINE's literal dense-GEMM leg, left fit()
                       in round 6: they run through the tests' Python choreography and ``bench.py`` only)
     device            HIP device ordinal (default: LOCAL_RANK or 0)
-    world             ``driver.LocalWorld`` / ``driver.TorchWorld`` (sharded runs; in a multi-process
-                      world the dense result goes to rank 0 only unless TorchWorld(handback="all"))
+    world             ``driver.LocalWorld`` / ``driver.TorchWorld``: who runs the update (``driver.py`` holds the worlds,
+                      the specs and the solvers' shared base, no loop: those are behind the C ABI).  Sharded runs; in a
+                      multi-process world the dense result goes to rank 0 only unless TorchWorld(handback="all")
     top_k             return, instead of the dense matrix, a long-format frame (node, rank,
                       neighbor, similarity) with the k most similar other nodes of every node,
                       selected on the device (no N x N transfer)
