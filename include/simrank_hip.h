@@ -491,6 +491,9 @@ SIMRANK_API int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* up
  *      "iterate_rows"    n (rows in the solver's order)
  *      "iterate_col_lo" / "iterate_col_hi"  0 / n (the columns the plan holds, solver's order)
  *      "ids"             device address of n int32: the caller's node id at each solver position (rows and columns)
+ * What leg 1 of the LATEST update left out (simrank_plan only; tuning "leg1_skip"):
+ *      "leg1_units"      workgroups of the one-launch leg 1 that own a unit (0: the launch was another kernel)
+ *      "leg1_skipped"    how many of them returned at once: their tiles of the transposed product are read by nobody
  * simrank_biplan_get answers the same keys per group (layout 0).  simrank_shardplan_get answers them for the rank's
  * column block: layout 1 (f32 row-major, "iterate_stride" = ld) or 2 (fp16-held, "iterate_stride" = rows_pad), n rows,
  * columns [col_lo, col_hi) of the solver's order; the block's column ids are "ids" + col_lo (the same values as
@@ -708,6 +711,12 @@ SIMRANK_API int simrank_shardbiplan_destroy(simrank_shardbiplan* bp);
  *      "restrict_support" SimRank++ leg 2 restricted to supp(E) (lane groups whose 32 evidence counts are all zero
  *                 skip their gathers), decided when a plan is created: 1 always (when evidence is given), 0 never,
  *                 -1 (default) when fewer than half of the 32-column evidence segments are live
+ *      "leg1_skip" 0/1  (default 1) a one-matrix plan's one-launch leg 1 leaves out the units of the transposed product
+ *                 that the upper-triangle leg 2 of the same update never reads (decided per update; never with an
+ *                 asymmetric prior, fp16-held matrices, another leg-1 kernel, or through simrank_spmm_blocked)
+ *      "leg1_order" the one-matrix plan's node order: 1 rows of equal length in the order of their first referencing row
+ *                 (what makes such units common), 0 the stable length order of the sharded plans (the same bits as their
+ *                 loops), -1 (default) the former from 16384 nodes on, where a fit repays the extra sorts
  *      "dense_sym" dense part in the upper-triangle form of leg 2: 1 always, 0 never, -1 when
  *                 the dense sets hold at least half of the entries
  *      "sym_desc" 0/1  upper-triangle leg 2: an XCD takes its panels in descending order (default 1)

@@ -982,6 +982,11 @@ int simrank_set_tuning(const char* key, int64_t value) {
     } else if (!strcmp(key, "restrict_support")) {
         SR_REQUIRE(value >= -1 && value <= 1, "restrict_support must be -1 (automatic), 0 or 1");
         t.restrict_support = value;
+    } else if (!strcmp(key, "leg1_skip")) {
+        t.leg1_skip = value ? 1 : 0;
+    } else if (!strcmp(key, "leg1_order")) {
+        SR_REQUIRE(value >= -1 && value <= 1, "leg1_order must be -1 (by the graph's size), 0 or 1");
+        t.leg1_order = value;
     } else {
         SR_REQUIRE(false, "unknown tuning key '%s'", key);
     }
@@ -1027,6 +1032,8 @@ int simrank_get_tuning(const char* key, int64_t* value) {
     else if (!strcmp(key, "dense_terms")) *value = t.dense_terms;
     else if (!strcmp(key, "probe_mask")) *value = t.probe_mask;
     else if (!strcmp(key, "restrict_support")) *value = t.restrict_support;
+    else if (!strcmp(key, "leg1_skip")) *value = t.leg1_skip;
+    else if (!strcmp(key, "leg1_order")) *value = t.leg1_order;
     else SR_REQUIRE(false, "unknown tuning key '%s'", key);
     return SIMRANK_OK;
 }

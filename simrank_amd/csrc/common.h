@@ -92,6 +92,12 @@ struct Tuning {
     int64_t fuse_sym = -1;   // (round 6) leg 2 of a symmetric update as ONE launch too (fused.hip, SYM: matrix cores + gathers +
                              // epilogue + both stores of a tile): 1 wherever it applies, 0 never, -1 where the dense sets hold at
                              // least half of the pattern's entries (MovieLens-shaped graphs: the two-launch leg's second pass)
+    int64_t leg1_skip = 1;   // a one-matrix plan's leg 1 returns from the units of Tt that the triangle-form leg 2 behind it never
+                             // reads (FusedArgs::first_block; decided per update in side_leg_pair); 0: every unit is computed
+    int64_t leg1_order = -1; // ... and its node order puts rows of equal length in the order of their first referencing row, which is
+                             // what makes such units common (planprep.hip): 1 always, 0 never (the stable length order of the
+                             // sharded plans: the same bits as their loops), -1 from kSpeculateBelow nodes on — below, an update
+                             // takes microseconds and a fit never repays the two extra sorts of plan_prepare
     int64_t dense_lazy = 0;  // (set by simrank_plan_create, not a knob) the graph's only launch that could use the dense-block
                              // plan is the upper-triangle leg 2: build it only if that leg would take it (dense_sym), i.e. skip
                              // the 256-byte-per-column fragment image and its upload on power-law graphs (8 ms at N = 65536)
@@ -167,7 +173,15 @@ struct PlanPrep {
     std::vector<int32_t> rp, cl;            // the pattern in the solver's order
     std::vector<float> rs;
     bool asym = false;                      // the prior is not symmetric: un-fused epilogue (SimRank.py:453 on asymmetric iterates)
+    std::vector<int32_t> first_block;       // plan_prepare only: per 32-node panel, the first 128-row block of leg 1 that a
+                                            // triangle-form leg 2 reads (first_block_table)
 };
+// "nobody references any node of the panel": every block lies before it
+constexpr int32_t kLeg1Never = 0x7FFFFFFF;
+// per 32-node panel of the order the pattern (rp, cl) is in: min over its nodes i of first(i) / 128, first(i) = the first row
+// whose list holds i (kLeg1Never: none).  Leg 1's unit (128-row block b, panel P) is read by no triangle-form leg 2 iff
+// b < first_block[P] (planprep.hip)
+void first_block_table(int64_t n, const int32_t* rp, const int32_t* cl, std::vector<int32_t>& first_block);
 struct BiPlanPrep {
     std::vector<int32_t> rowptr21, col21;   // the group-2 pattern (transpose), caller's order
     std::vector<int32_t> ord[2], inv[2];
@@ -275,6 +289,7 @@ struct simrank_fused_plan {
                                     // rowscale bits
     uint16_t* sids16 = nullptr;     // gather id stream, 64 per round (0xFFFF: no neighbour), or
     int32_t* sids32 = nullptr;      //              32-bit ids (-1: no neighbour)
+    std::vector<int32_t> unit_last; // host: last 128-row block of every unit, ascending (fused_leg1_counts)
 };
 
 #ifdef SIMRANK_EXPERIMENT_FUSED2
@@ -306,8 +321,22 @@ constexpr int kFB = 128;          // rows per block of the one-launch plan
 constexpr int kSub = 4;           // blocks a unit without a dense set may hold
 void free_fused_plan(simrank_fused_plan* p);
 int build_fused_plan(simrank_graph* g, const int32_t* rowptr, const int32_t* col, const float* rowscale);
+// first_block (device, one int32 per panel of L, or NULL: nothing skipped): a workgroup whose unit ends before block
+// first_block[panel] returns at once and stores nothing
 int launch_fused_trans(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t L, float* Y,
-                       int64_t y_rows_pad, hipStream_t st);
+                       int64_t y_rows_pad, hipStream_t st, const int32_t* first_block = nullptr);
+// workgroups of a leg-1 launch over L columns that have a unit (the grid's padding panels not counted), and how many of
+// them the host copy of such a table sends home
+void fused_leg1_counts(const simrank_graph* g, int64_t L, const int32_t* first_block_host, int64_t* units, int64_t* skipped);
+// spmm.hip, for side.h: would this epilogue launch on panel-blocked operands (simrank_spmm_blocked's arguments, leg 2 of an
+// update) run in a triangle form that leaves the dead units of first_block_table unread?  Evaluated from the graph's knobs
+// exactly as the dispatch of that launch evaluates them; launches nothing.
+int spmm_blocked_is_triangle(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t n_cols_x, float* Y,
+                             int64_t y_rows_pad, const simrank_epilogue* ep, bool* triangle);
+// ... and leg 1 (simrank_spmm_blocked with transpose_out = 1, no epilogue) with such a table: used only where the launch is
+// the one-launch kernel (*skipping says whether it was), ignored by every other leg 1
+int spmm_blocked_leg1(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t n_cols_x, float* Y,
+                      int64_t y_rows_pad, const int32_t* first_block, bool* skipping, void* stream);
 bool fused_sym_applies(const simrank_graph* g, int64_t x_rows_pad, int64_t L, int64_t y_rows_pad);
 int launch_fused_sym(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t L, float* Y, int64_t y_rows_pad,
                      float coef, float lbd, double eps, const uint8_t* ev, const float* ap, const float* prev,

@@ -114,6 +114,9 @@ struct FusedArgs {
     const float* prev;        // previous iterate (the count), or NULL
     unsigned long long* n_changed;
     int32_t set_diag, count_any;
+    // ---- leg 1 in front of a triangle-form leg 2 (planprep.hip first_block_table): per panel the first 128-row block whose tile
+    // that leg 2 reads; NULL: every unit is computed.  (Last: the offsets of the fields above are what they were.)
+    const int32_t* first_block;
 };
 
 #ifndef SIMRANK_HOST_ONLY          // (the sanitizer build of the host logic has no device code: common.h)
@@ -186,6 +189,12 @@ __global__ __launch_bounds__(256, SYM ? SIMRANK_FUSED_LB_SYM : SIMRANK_FUSED_LB)
     const int n_sub_all = un[8];
     const int n_sub_sym = SYM ? min(n_sub_all, int((c0 + 31) >> 7) - b0 + 1) : n_sub_all;
     if (SYM && n_sub_sym <= 0) return;
+    // (leg 1) a unit whose last block lies before the panel's first live one holds tiles nobody reads: nothing is loaded, nothing
+    // stored — one uniform load and a compare, ahead of every load of the prologue.  The units of a split block share the block and
+    // decide alike (as above: no ticket is ever short); a grouped unit is skipped whole or not at all.
+    if constexpr (!SYM) {
+        if (p.first_block && b0 + n_sub_all - 1 < p.first_block[panel]) return;
+    }
     const int g = lane >> 3, q = lane & 7, gbase = lane & ~7;
     const uint32_t qoff = uint32_t(q) * 16u;
 
@@ -1193,6 +1202,9 @@ int build_fused_plan(simrank_graph* g, const int32_t* rowptr, const int32_t* col
     pl->nnz_covered = covered;
     pl->r_nnz = r_nnz;
     pl->ids16 = ids16 ? 1 : 0;
+    pl->unit_last.reserve(ulist.size());
+    for (const Unit& u : ulist) pl->unit_last.push_back(u.b0 + u.nsub - 1);
+    std::sort(pl->unit_last.begin(), pl->unit_last.end());
     // (one quad of padding behind the last set: the kernel requests the first ids and pattern bits of a unit's share of its
     // set before it knows whether the unit has one — a unit of the last blocks without a set reads here)
     dcols.resize(dcols.size() + 64, 0);
@@ -1306,7 +1318,7 @@ static int launch_fused(const simrank_graph* g, FusedArgs& a, hipStream_t st, bo
 
 // Tt (panel-blocked, y_rows_pad rows per panel) = (diag(rowscale) . A . X)^T, X panel-blocked
 int launch_fused_trans(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t L, float* Y,
-                       int64_t y_rows_pad, hipStream_t st) {
+                       int64_t y_rows_pad, hipStream_t st, const int32_t* first_block) {
     SR_REQUIRE(g->fused, "graph has no fused plan");
     SR_REQUIRE(aligned16(X) && aligned16(Y), "fused leg needs 16-byte aligned operands");
     SR_REQUIRE(x_rows_pad >= g->n_cols && (x_rows_pad + 1) * 128 < (int64_t(1) << 31) && x_rows_pad < (int64_t(1) << 24) - 1,
@@ -1319,7 +1331,20 @@ int launch_fused_trans(const simrank_graph* g, const float* X, int64_t x_rows_pa
     a.x_pitch = 128;
     a.x_bytes = int32_t(x_rows_pad * 128);
     a.x_sentinel = (int32_t)x_rows_pad;
+    a.first_block = first_block;
     return launch_fused(g, a, st);
+}
+
+void fused_leg1_counts(const simrank_graph* g, int64_t L, const int32_t* first_block_host, int64_t* units, int64_t* skipped) {
+    *units = *skipped = 0;
+    const simrank_fused_plan* pl = g->fused;
+    if (!pl) return;
+    const int64_t n_panels = (L + 31) / 32;
+    *units = n_panels * pl->n_units;
+    if (!first_block_host) return;
+    // the kernel's test, unit by unit: last block < first_block[panel]
+    for (int64_t p = 0; p < n_panels; ++p)
+        *skipped += std::lower_bound(pl->unit_last.begin(), pl->unit_last.end(), first_block_host[p]) - pl->unit_last.begin();
 }
 
 // Leg 2 of a symmetric panel-blocked update in one launch (SYM): Y (M x M, M = n_rows(g) = L) = epilogue(diag(rowscale) . A . X),

@@ -6,8 +6,8 @@
 //         if converged(old, new): break
 //         new = E * C * W.S.W^T (+ lbd A); diag <- 1
 //
-// as two launches per update (leg 1: fused_trans_kernel, leg 2: upper-triangle gather with the fused
-// epilogue and count), with update k + 1 queued BEFORE the count of update k is read (graphs below 16384 nodes,
+// as two launches per update (leg 1: fused_trans_kernel, without the units of the transposed product that leg 2 never
+// reads; leg 2: upper-triangle gather with the fused epilogue and count), with update k + 1 queued BEFORE the count of update k is read (graphs below 16384 nodes,
 // where an update is short; common.h kSpeculateBelow): the host never
 // leaves the device idle to learn whether it may go on, and when the count says "converged" the
 // speculative update is simply not adopted (it wrote the buffer of the iterate before last).
@@ -172,6 +172,19 @@ int simrank_plan_create(int64_t n, int64_t nnz, const int32_t* rowptr, const int
     };
     rc = counters();
     if (!rc) rc = side_alloc(a, pp.ord, pp.inv, p->stream);
+    if (!rc && !a.half) {
+        // the units of leg 1 that a triangle-form leg 2 never reads (planprep.hip first_block_table; side_leg_pair decides per
+        // update whether they are left out): one int32 per panel, the plan's, freed with the side
+        auto table = [&]() -> int {
+            const size_t bytes = pp.first_block.size() * sizeof(int32_t);
+            SIDE_HIP(pool_hip_alloc((void**)&a.first_block, bytes));
+            SIDE_HIP(hipMemcpyAsync(a.first_block, pp.first_block.data(), bytes, hipMemcpyHostToDevice, p->stream));
+            SIDE_HIP(hipStreamSynchronize(p->stream));
+            a.first_block_host = pp.first_block;
+            return SIMRANK_OK;
+        };
+        rc = table();
+    }
     if (rc) return fail(rc);
     lap("matrices allocated, orders uploaded, stream drained");
     if (opt->evidence) rc = side_restrict(a, p->stream);

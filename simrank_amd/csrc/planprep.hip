@@ -1,6 +1,7 @@
 // Host-only half of simrank_plan_create / simrank_biplan_create: argument validation, the solver's node
-// order (ascending row length), the renamed CSR patterns, the transposed pattern of the
-// bipartite plans.  No HIP call in here: `make asan` compiles this file for the host and tools/host/
+// order (ascending row length; the one-matrix plan: equal lengths by first referencing row, with the
+// table of leg-1 units nobody reads), the renamed CSR patterns, the transposed pattern of the bipartite plans.
+// No HIP call in here: `make asan` compiles this file for the host and tools/host/
 // host_fuzz.cpp throws malformed inputs at it (non-monotone rowptr, columns out of range or repeated,
 // asymmetric / non-finite priors), expecting SIMRANK_ERR_INVALID and no out-of-bounds read.
 // Replaces nothing of the reference by itself: it is what `_create_graph` (SimRank.py:24-52, :168-200) does to
@@ -119,6 +120,52 @@ static void length_order(int64_t n, const int32_t* rowptr, bool reorder, std::ve
     for (int64_t r = 0; r < n; ++r) inv[(size_t)ord[(size_t)r]] = (int32_t)r;
 }
 
+// The one-matrix plan's order: rows of EQUAL length are put in the order of first(i), the first row of the
+// solver's order whose list holds node i (a node nobody references: last).  Leg 2 in its triangle form reads row i of the
+// transposed product only from panel first(i) / 32 on, so 32 neighbouring nodes whose first(i) are alike leave leg 1 whole
+// 128 x 32 units it need not compute (first_block_table below).  first() depends on the order it is used to refine: two
+// passes from the stable length order, each a stable sort by (length, first under the order so far) — the figures stop
+// moving after the second, the result is deterministic, and ascending length stays exact.  Nothing needs a fixed point:
+// the table is computed from the final order.
+static void refine_by_first_reference(int64_t n, const int32_t* rowptr, const int32_t* col, std::vector<int32_t>& ord,
+                                      std::vector<int32_t>& inv) {
+    std::vector<int32_t> first((size_t)n);
+    for (int pass = 0; pass < 2; ++pass) {
+        std::fill(first.begin(), first.end(), (int32_t)n);
+        for (int64_t r = 0; r < n; ++r) {
+            const int32_t a = ord[(size_t)r];
+            for (int32_t j = rowptr[a]; j < rowptr[a + 1]; ++j)
+                if (first[(size_t)col[j]] == (int32_t)n) first[(size_t)col[j]] = (int32_t)r;
+        }
+        std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) {
+            const int32_t lx = rowptr[x + 1] - rowptr[x], ly = rowptr[y + 1] - rowptr[y];
+            return lx != ly ? lx < ly : first[(size_t)x] < first[(size_t)y];
+        });
+    }
+    for (int64_t r = 0; r < n; ++r) inv[(size_t)ord[(size_t)r]] = (int32_t)r;
+}
+
+// first_block[P], P a 32-node panel of the solver's order (rp, cl: the pattern in that order): the smallest first(i) / 128
+// over the panel's nodes, kLeg1Never when nobody references any of them.  Leg 1's unit (128-row block b, panel P) holds
+// Tt[i, 128 b .. 128 b + 127] for the panel's nodes i; a triangle-form leg 2 reads Tt[i, panel q] only for rows a with
+// i in N(a) that compute panel q, and those are
+//   * gather3_kernel<kSym> (spmm.hip, `rb = row0 & ~(RT - 1); if (rb > c0) nrows = 0;`): the 32-row tile of a computes
+//     panel q iff 32 (a / 32) <= 32 q, so a >= first(i) reads panels q >= first(i) / 32 >= 4 (first(i) / 128) only;
+//   * fused_trans_kernel<., SYM> (fused.hip, `n_sub_sym = min(n_sub_all, int((c0 + 31) >> 7) - b0 + 1)`): the 128-row block
+//     of a computes panel q iff a / 128 <= q / 4, so again q / 4 >= first(i) / 128.
+// Either way the columns of Tt left of 128 first_block[P] are never read in the panel's rows: unit (b, P) is dead iff
+// b < first_block[P].  Whole 128-row blocks on purpose — the rule both kernels satisfy.  Valid for ANY order (reorder = 0 too).
+void first_block_table(int64_t n, const int32_t* rp, const int32_t* cl, std::vector<int32_t>& first_block) {
+    std::vector<int32_t> first((size_t)n, kLeg1Never);
+    for (int64_t a = 0; a < n; ++a)
+        for (int32_t j = rp[a]; j < rp[a + 1]; ++j)
+            if (first[(size_t)cl[j]] == kLeg1Never) first[(size_t)cl[j]] = (int32_t)a;
+    first_block.assign((size_t)((n + 31) / 32), kLeg1Never);
+    for (int64_t i = 0; i < n; ++i)
+        if (first[(size_t)i] != kLeg1Never)
+            first_block[(size_t)(i >> 5)] = std::min(first_block[(size_t)(i >> 5)], first[(size_t)i] / 128);
+}
+
 // the ascending order `ord` dealt to `deal` shards in runs of 128 (32) nodes when n divides evenly (driver.dealt_order)
 static void deal_order(int64_t n, int32_t deal, std::vector<int32_t>& ord, std::vector<int32_t>& inv) {
     if (deal <= 1 || n % (32 * int64_t(deal))) return;
@@ -142,7 +189,20 @@ int plan_prepare(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* c
     if (!rc) rc = check_prior(opt->apriori, opt->ld_apriori, n, 1, opt->storage_fp16 != 0, &out->asym);
     if (rc) return rc;
     length_order(n, rowptr, opt->reorder != 0, out->ord, out->inv);
-    return renamed(n, rowptr, col, rowscale, out->ord, out->inv, nnz, "", out->rp, out->cl, out->rs);
+    // (only where a leg 1 of this plan can ever skip — the knobs that rule the triangle form out, an asymmetric prior and fp16-held
+    // matrices leave it the stable length order, the order of the sharded plans: such a plan stays bit-equal to their loops —
+    // and, unless tuning "leg1_order" says otherwise, only where it pays: the two passes cost 5 ms of a plan_create at N = 32768
+    // (1 M entries) against 0.41 ms saved per update, repaid by the twelfth update of a fit; at N = 8192 leg 1 saves 0.02 ms per
+    // update and a fit of fifteen never repays them.  The line is kSpeculateBelow, where an update starts to take milliseconds.
+    // Below it a one-GPU fit therefore keeps the sharded loops' order and differs from them by the triangle form's mirrored
+    // tiles only, not by the rounding of every sum.)
+    const Tuning t = tuning_snapshot();
+    const bool refine = t.leg1_order > 0 || (t.leg1_order < 0 && n >= kSpeculateBelow);
+    if (opt->reorder && refine && t.triangle && t.fuse == 1 && n >= 64 && !out->asym && !opt->storage_fp16)
+        refine_by_first_reference(n, rowptr, col, out->ord, out->inv);
+    rc = renamed(n, rowptr, col, rowscale, out->ord, out->inv, nnz, "", out->rp, out->cl, out->rs);
+    if (!rc) first_block_table(n, out->rp.data(), out->cl.data(), out->first_block);
+    return rc;
 }
 
 int shard_prepare(int64_t n, int64_t nnz, const int32_t* rowptr, const int32_t* col, const float* rowscale,

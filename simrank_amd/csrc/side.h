@@ -39,6 +39,13 @@ struct side_t {
     int32_t restrict_support = 0;
     int32_t half = 0;                          // 1: S and Tt are fp16 on 64-column panels (half.hip), value x kHalfScale
     int cur = 0;                               // S[cur] is the current iterate
+    // leg 1 in front of a triangle-form leg 2 (simrank_plan only; planprep.hip first_block_table): per panel of Tt's rows the
+    // first 128-row block of leg 1 that leg 2 reads — device copy for the kernel, host copy for the counts
+    int32_t* first_block = nullptr;
+    std::vector<int32_t> first_block_host;
+    int64_t leg1_units = 0, leg1_skipped = 0;  // of the latest update: workgroups of the one-launch leg 1 that have a unit, and
+                                               // how many of them returned at once ("leg1_units", "leg1_skipped")
+    int64_t dead_units = -1;                   // what the table skips of such a launch (-1: not counted yet)
 };
 
 // an n x n f32 matrix on 32-column panels: the prior, and the widened copy of an fp16-held iterate
@@ -57,9 +64,10 @@ inline void side_shape(side_t& a, int64_t n, int64_t k, bool half) {
 }
 
 // The matrices and both node orders; the stream is drained (inv may be a host vector about to go away).
-// (no memset: reset fills S[0] — zeros and the diagonal —, every update writes all of Tt and of the other iterate before
-// anything reads them, and the padding rows and columns of a panel are read by nobody: lanes that hold columns past the
-// edge compute on whatever is there and never store.  Three 17 GiB memsets were 10 ms of a config-5 set-up.)
+// (no memset: reset fills S[0] — zeros and the diagonal —, every update writes all of the other iterate and every tile of Tt
+// that its leg 2 reads before anything reads them — a leg 1 in front of a triangle-form leg 2 leaves the tiles that leg never
+// reads as they are (side_leg_pair) —, and the padding rows and columns of a panel are read by nobody: lanes that hold
+// columns past the edge compute on whatever is there and never store.  Three 17 GiB memsets were 10 ms of a config-5 set-up.)
 inline int side_alloc(side_t& a, const std::vector<int32_t>& ord, const std::vector<int32_t>& inv, hipStream_t st) {
     const size_t ids = size_t(a.n) * sizeof(int32_t);
     for (float** b : {&a.S[0], &a.S[1]}) SIDE_HIP(pool_hip_alloc((void**)b, a.mat_bytes));
@@ -82,7 +90,7 @@ inline void side_trim(side_t& a) {
 
 inline void side_free(side_t& a) {
     side_trim(a);
-    (void)pool_free(a.ev); (void)pool_free(a.inv); (void)pool_free(a.ord_dev);
+    (void)pool_free(a.ev); (void)pool_free(a.inv); (void)pool_free(a.ord_dev); (void)pool_free(a.first_block);
     simrank_graph_destroy(a.g);
 }
 
@@ -143,18 +151,14 @@ inline int side_prior(side_t& a, const float* apriori, int64_t ld_apriori, hipSt
 // from_identity: S_o is the identity, so leg 1 is W^T written directly — the same bits without a gather.
 // asym: the iterates are not symmetric (a prior that is not): leg 2 = leg 1's launch again, then the epilogue as a pass
 // of its own.  stamp() is called before leg 1, between the legs and after leg 2 (simrank_plan_set_timing).
+// A side with a first_block table (simrank_plan): where the leg 2 of THIS update is a triangle form — asked of spmm.hip's
+// dispatch with leg 2's own arguments, from the knobs as they are now — leg 1 leaves out the units that form never reads
+// (tuning "leg1_skip").  Never for the identity's leg 1, an asymmetric prior (leg 2 runs leg 1's kernel over all of Tt),
+// fp16-held matrices, or a leg 1 that is not the one-launch kernel.
 template <class Stamp>
 int side_leg_pair(side_t& a, const side_t& o, bool from_identity, bool asym, double eps, int32_t exact_count,
                   unsigned long long* counters, unsigned long long* host_slot, hipStream_t st, Stamp&& stamp) {
     const int nx = a.cur ^ 1;
-    int rc = stamp();
-    if (rc) return rc;
-    rc = from_identity ? (a.half ? identity_leg1_blocked_h16(a.g, reinterpret_cast<uint16_t*>(a.Tt), a.k_rows_pad, kHalfScale, st)
-                                 : identity_leg1_blocked(a.g, a.Tt, a.k_rows_pad, st))
-         : a.half ? simrank_spmm_blocked_h16(a.g, o.S[o.cur], o.rows_pad, a.k, a.Tt, a.k_rows_pad, 1, nullptr, 0, kHalfScale, st)
-                  : simrank_spmm_blocked(a.g, o.S[o.cur], o.rows_pad, a.k, a.Tt, a.k_rows_pad, 1, nullptr, st);
-    if (!rc) rc = stamp();
-    if (rc) return rc;
     simrank_epilogue ep{};
     ep.coef = a.coef;
     ep.lbd = a.lbd;
@@ -171,6 +175,31 @@ int side_leg_pair(side_t& a, const side_t& o, bool from_identity, bool asym, dou
     ep.symmetric = 1;
     ep.restrict_support = a.restrict_support;
     ep.count_any = exact_count ? 0 : 1;
+    const int32_t* skip = nullptr;
+    if (a.first_block && a.g->tun.leg1_skip && !from_identity && !asym && !a.half) {
+        bool triangle = false;
+        const int rct = spmm_blocked_is_triangle(a.g, a.Tt, a.k_rows_pad, a.n, a.S[nx], a.rows_pad, &ep, &triangle);
+        if (rct) return rct;
+        if (triangle) skip = a.first_block;
+    }
+    int rc = stamp();
+    if (rc) return rc;
+    bool skipping = false;
+    rc = from_identity ? (a.half ? identity_leg1_blocked_h16(a.g, reinterpret_cast<uint16_t*>(a.Tt), a.k_rows_pad, kHalfScale, st)
+                                 : identity_leg1_blocked(a.g, a.Tt, a.k_rows_pad, st))
+         : a.half ? simrank_spmm_blocked_h16(a.g, o.S[o.cur], o.rows_pad, a.k, a.Tt, a.k_rows_pad, 1, nullptr, 0, kHalfScale, st)
+                  : spmm_blocked_leg1(a.g, o.S[o.cur], o.rows_pad, a.k, a.Tt, a.k_rows_pad, skip, &skipping, st);
+    a.leg1_units = a.leg1_skipped = 0;
+    if (!rc && a.first_block && !from_identity && !a.half) {
+        int64_t dead = 0;
+        fused_leg1_counts(a.g, a.k, skipping ? a.first_block_host.data() : nullptr, &a.leg1_units, &dead);
+        if (skipping) {
+            if (a.dead_units < 0) a.dead_units = dead;
+            a.leg1_skipped = a.dead_units;
+        }
+    }
+    if (!rc) rc = stamp();
+    if (rc) return rc;
     if (asym) {
         // S is not symmetric (SimRank.py:453, :488, :491 with a prior that is not): W . Tt is the TRANSPOSE of W S_o W^T, so
         // leg 2 is leg 1's launch on Tt — X -> (W X)^T, the one-launch kernel again — and the epilogue (coefficient,
@@ -290,6 +319,8 @@ inline int side_get(const side_t& a, const char* key, int64_t* value) {
     else if (!strcmp(key, "iterate_rows") || !strcmp(key, "iterate_col_hi")) *value = a.n;
     else if (!strcmp(key, "iterate_col_lo")) *value = 0;
     else if (!strcmp(key, "ids")) *value = (int64_t)(uintptr_t)a.ord_dev;
+    else if (!strcmp(key, "leg1_units")) *value = a.leg1_units;
+    else if (!strcmp(key, "leg1_skipped")) *value = a.leg1_skipped;
     else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }

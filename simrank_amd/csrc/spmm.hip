@@ -2078,10 +2078,20 @@ int simrank_fill_identity(float* S, int64_t n_rows, int64_t n_cols, int64_t ld, 
     return SIMRANK_OK;
 }
 
+// what a plan's update asks of the dispatch beyond the public arguments (side.h through spmm_blocked_is_triangle /
+// spmm_blocked_leg1 below): `dry`: launch nothing, queue nothing, answer in `triangle` whether this epilogue launch would be
+// a triangle form whose reads the table of planprep.hip's first_block_table describes — gather3_kernel<kSym> on the plain
+// pattern, or the one-launch leg 2; NOT the dense_tiles + gather3 pair, whose matrix-core launch works per 256 output columns
+// and reads left of the diagonal block.  `first_block`: that table for a leg 1, used (`skipping`) by the one-launch kernel only.
+struct Leg1Skip {
+    bool dry = false, triangle = false, skipping = false;
+    const int32_t* first_block = nullptr;
+};
+
 static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_t n_cols_x,
                      float* Y, int64_t ldy, int32_t transpose_out, int64_t t_block, int64_t t_pad,
                      const simrank_epilogue* ep, void* stream, bool blocked, int64_t x_rows_pad,
-                     int64_t y_rows_pad) {
+                     int64_t y_rows_pad, Leg1Skip* sk = nullptr) {
     SR_REQUIRE(t_pad >= 0 && t_pad < 4096, "t_pad out of range");
     SR_REQUIRE(g && X && Y, "NULL argument");
     const Tuning& T = g->tun;        // the knobs as they were when the graph was created
@@ -2141,7 +2151,8 @@ static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_
         if (a.ev) vec_ok = vec_ok && (reinterpret_cast<uintptr_t>(a.ev) % 4 == 0) && a.ld_ev % 4 == 0;
         if (a.ap) vec_ok = vec_ok && aligned16(a.ap) && a.ld_ap % 4 == 0;
         if (a.prev) vec_ok = vec_ok && aligned16(a.prev) && a.ld_prev % 4 == 0;
-        if (a.prev) SR_HIP(hipMemsetAsync(a.n_changed, 0, sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS, st));
+        if (a.prev && !(sk && sk->dry))
+            SR_HIP(hipMemsetAsync(a.n_changed, 0, sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS, st));
     }
     // automatic choice (profiles/ sweep_r01.log): 32 rows per wave tile; 32-float panels for
     // the transposed leg (keeps its LDS tile at 17 KiB -> 7 workgroups per CU), 64 otherwise
@@ -2152,32 +2163,11 @@ static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_
     a.nt = (int32_t)T.stream_nt;
     const bool want_sym = ep && ep->symmetric && T.triangle && vec_ok && !transpose_out &&
                           n_cols_x == g->n_rows && ep->diag_col0 == 0 && g->n_rows >= 64;
-    // leg 1 of a panel-blocked update: one launch, matrix cores + gathers on the same panel slice (fused.hip)
-    // (measured against the two-launch leg: -13 % at K = 32768 power-law, -10 % Erdos-Renyi, -6 % at K = 65536)
-    if (blocked && transpose_out && g->fused && T.fuse && vec_ok && T.dense_terms == 3 && g->n_cols <= T.fuse_max_rows &&
-        (x_rows_pad + 1) * 128 < (int64_t(1) << 31)) {
-#ifdef SIMRANK_EXPERIMENT_FUSED2
-        if (T.fuse == 2 && g->fused2 && (g->fused2->n_pslots == 0 || (n_cols_x + 31) / 32 <= g->fused2->cap_panels))
-            return launch_fused2_trans(g, X, x_rows_pad, n_cols_x, Y, y_rows_pad, st);
-#endif
-        return launch_fused_trans(g, X, x_rows_pad, n_cols_x, Y, y_rows_pad, st);
-    }
-    // ... and of a rank of a sharded update: the same launch on its row-major column block, the result in the
-    // chunks of the all-to-all (round 4; tuning "fuse_shards")
-    if (!blocked && transpose_out && g->fused && T.fuse && T.fuse_shards && vec_ok && T.dense_terms == 3 &&
-        g->n_cols <= T.fuse_max_rows) {
-        // (one block with pitched rows, Y^T[c * ldy + a], is the chunked layout with t_pad = ldy - n_rows)
-        const int64_t tb = a.tstride ? g->n_rows : t_block, tp = a.tstride ? a.tstride - g->n_rows : t_pad;
-        if (fused_rowmajor_fits(g, X, ldx, n_cols_x, Y, tb, tp))
-            return launch_fused_trans_rowmajor(g, X, ldx, n_cols_x, Y, tb, tp, st);
-    }
     // leg 2 of a symmetric panel-blocked update in ONE launch where the dense sets carry it (round 6; tuning "fuse_sym"): the
     // matrix-core phase, the gathered remainder, the epilogue and both stores of a tile by the same workgroup — the two-launch
     // leg below hands the dense part's partial sums over through memory
-    if (blocked && want_sym && !transpose_out && ep && (!ep->restrict_support || T.fuse_sym > 0) &&
-        fused_sym_applies(g, x_rows_pad, n_cols_x, y_rows_pad))
-        return launch_fused_sym(g, X, x_rows_pad, n_cols_x, Y, y_rows_pad, a.coef, a.lbd, a.eps, a.ev, a.ap, a.prev, a.n_changed,
-                                a.set_diag, a.count_any, st);
+    const bool one_launch_sym = blocked && want_sym && !transpose_out && ep && (!ep->restrict_support || T.fuse_sym > 0) &&
+                                fused_sym_applies(g, x_rows_pad, n_cols_x, y_rows_pad);
     // the block-dense part goes to the matrix cores first; the gather then runs on the remainder
     // In the upper-triangle form only when the pattern is dense throughout (MovieLens-like: 87 % of
     // the entries in dense sets, leg 2 0.9 -> 0.4 ms): on a power-law pattern the long rows, which
@@ -2188,6 +2178,33 @@ static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_
         const int64_t mode = T.dense_sym;
         if (mode == 0 || (mode < 0 && 2 * dp->nnz_covered < g->nnz)) dp = nullptr;
     }
+    if (sk && sk->dry) {
+        sk->triangle = blocked && want_sym && (one_launch_sym || !dp);
+        return SIMRANK_OK;
+    }
+    // leg 1 of a panel-blocked update: one launch, matrix cores + gathers on the same panel slice (fused.hip)
+    // (measured against the two-launch leg: -13 % at K = 32768 power-law, -10 % Erdos-Renyi, -6 % at K = 65536)
+    if (blocked && transpose_out && g->fused && T.fuse && vec_ok && T.dense_terms == 3 && g->n_cols <= T.fuse_max_rows &&
+        (x_rows_pad + 1) * 128 < (int64_t(1) << 31)) {
+#ifdef SIMRANK_EXPERIMENT_FUSED2
+        if (T.fuse == 2 && g->fused2 && (g->fused2->n_pslots == 0 || (n_cols_x + 31) / 32 <= g->fused2->cap_panels))
+            return launch_fused2_trans(g, X, x_rows_pad, n_cols_x, Y, y_rows_pad, st);
+#endif
+        if (sk) sk->skipping = sk->first_block != nullptr;
+        return launch_fused_trans(g, X, x_rows_pad, n_cols_x, Y, y_rows_pad, st, sk ? sk->first_block : nullptr);
+    }
+    // ... and of a rank of a sharded update: the same launch on its row-major column block, the result in the
+    // chunks of the all-to-all (round 4; tuning "fuse_shards")
+    if (!blocked && transpose_out && g->fused && T.fuse && T.fuse_shards && vec_ok && T.dense_terms == 3 &&
+        g->n_cols <= T.fuse_max_rows) {
+        // (one block with pitched rows, Y^T[c * ldy + a], is the chunked layout with t_pad = ldy - n_rows)
+        const int64_t tb = a.tstride ? g->n_rows : t_block, tp = a.tstride ? a.tstride - g->n_rows : t_pad;
+        if (fused_rowmajor_fits(g, X, ldx, n_cols_x, Y, tb, tp))
+            return launch_fused_trans_rowmajor(g, X, ldx, n_cols_x, Y, tb, tp, st);
+    }
+    if (one_launch_sym)
+        return launch_fused_sym(g, X, x_rows_pad, n_cols_x, Y, y_rows_pad, a.coef, a.lbd, a.eps, a.ev, a.ap, a.prev, a.n_changed,
+                                a.set_diag, a.count_any, st);
     if (dp) {
         DenseUse use;
         const int rc = launch_dense_tiles(g, X, blocked ? -x_rows_pad : ldx, n_cols_x, want_sym, st, &use);
@@ -2368,6 +2385,30 @@ int simrank_spmm_blocked(const simrank_graph* g, const float* X, int64_t x_rows_
                "padded row counts %lld / %lld too small", (long long)x_rows_pad, (long long)y_rows_pad);
     return spmm_impl(g, X, 32, n_cols_x, Y, 32, transpose_out, 0, 0, ep, stream, true, x_rows_pad, y_rows_pad);
 }
+
+}  // extern "C"
+
+namespace simrank {
+int spmm_blocked_is_triangle(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t n_cols_x, float* Y,
+                             int64_t y_rows_pad, const simrank_epilogue* ep, bool* triangle) {
+    Leg1Skip sk;
+    sk.dry = true;
+    const int rc = spmm_impl(g, X, 32, n_cols_x, Y, 32, 0, 0, 0, ep, nullptr, true, x_rows_pad, y_rows_pad, &sk);
+    *triangle = rc == SIMRANK_OK && sk.triangle;
+    return rc;
+}
+
+int spmm_blocked_leg1(const simrank_graph* g, const float* X, int64_t x_rows_pad, int64_t n_cols_x, float* Y,
+                      int64_t y_rows_pad, const int32_t* first_block, bool* skipping, void* stream) {
+    Leg1Skip sk;
+    sk.first_block = first_block;
+    const int rc = spmm_impl(g, X, 32, n_cols_x, Y, 32, 1, 0, 0, nullptr, stream, true, x_rows_pad, y_rows_pad, &sk);
+    *skipping = rc == SIMRANK_OK && sk.skipping;
+    return rc;
+}
+}  // namespace simrank
+
+extern "C" {
 
 static int epilogue_apply_impl(const float* Q, int64_t ldq, float* Y, int64_t ldy, int64_t n_rows,
                                int64_t n_cols, const simrank_epilogue* ep, void* stream, int64_t rows_pad) {
