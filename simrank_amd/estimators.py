@@ -642,6 +642,53 @@ class _KeptModel:
             return pd.DataFrame(labels.T.reshape(len(index), len(ts)), index=index, columns=[float(x) for x in ts], dtype=np.int64)
         return self._all_sides(make)
 
+    def linkage(self, min_similarity=None):
+        """The single-linkage dendrogram: every ``components(t)`` at once.  Two different nodes a, b fall together at the
+        height ``w(a, b) = max(S[a, b], S[b, a])``, compared as ``components`` compares (float64 on the bits the dense frame
+        holds); a NaN entry is no entry, -0.0 and +0.0 are one height, reported as +0.0.
+
+        -> DataFrame (left, right: int64; similarity: float64; size: int64) in the shape of a SciPy linkage matrix, with
+        similarities that fall where SciPy's distances rise (pass ``1 - similarity`` on).  Cluster ids below N are
+        leaves, the positions in the dense frame's label order; row i forms cluster N + i of ``size`` members.  N - 1
+        rows when everything joins; fewer when NaN isolates nodes or ``min_similarity`` (a finite number: entries with
+        ``w < min_similarity`` are not used) stops the tree.
+
+        The table is a function of the matrix alone, ties included.  With h1 > h2 > ... the distinct heights: every
+        component of ``components(h_j)`` that unites m >= 2 components c1 .. cm of ``components(h_(j-1))``, taken in the
+        order of their smallest member, gives the m - 1 rows (c1, c2) -> x1, (x1, c3) -> x2, ...; the new components of
+        one height come in the order of their smallest member.  ``left`` is the cluster grown so far.
+
+        A maximum spanning forest found on the device by Boruvka's rounds (libsimrank_linkage.so): at most
+        ceil(log2 N) + 1 rounds, each one sweep of the iterate in place (two for a float64 model), integer atomics only;
+        12 N bytes cross, and the host orders the N - 1 edges.  A pruned model is answered on the host from its lists and
+        needs ``min_similarity > 0``: its absent entries are +0.0 and tie everything at 0.  The model is left unchanged.
+        A tuple of two for the bipartite classes."""
+        from . import _linkage
+        floor = _linkage.check_floor(min_similarity)
+        if self._model is not None:
+            _linkage.check_solver(self._model[0], floor)
+
+        def make(solver, j, lab):
+            _, left, right, sim, size = _linkage.table(solver, j, floor)
+            return pd.DataFrame(dict(zip(_linkage.COLUMNS, (left, right, sim, size))))
+        return self._all_sides(make)
+
+    def cut(self, Z, t=None, n_clusters=None, group=None):
+        """Flat clusters from a table ``Z`` of ``linkage`` (of ``group=1 | 2`` for the bipartite classes): host arithmetic
+        on Z and the model's labels.  Exactly one of ``t`` and ``n_clusters``:
+
+        ``t`` (a finite number) applies every row with ``similarity >= t``: for ``t`` at or above the ``min_similarity``
+        Z was made with, exactly ``components(t)``.  ``n_clusters=k`` applies the first N - k rows and leaves k clusters;
+        a ValueError when Z has fewer rows.  Within a tie of similarities the split follows the table's canonical order:
+        the tied merges of components with the smallest members come first.
+
+        -> Series "component" (int64) over the dense frame's labels, numbered 0, 1, 2, ... in the order of each
+        component's first member, as ``components`` numbers."""
+        from . import _linkage
+        t, k = _linkage.check_cut(t, n_clusters)
+        _, _, labels = self._kept(group)
+        return pd.Series(_linkage.cut_labels(len(labels), Z, t, k), index=pd.Index(labels), name="component", dtype=np.int64)
+
     def compact(self, precision=None):
         """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense
         frame's order (libsimrank_model.so), then the plan's matrices are released (the evidence counts stay, so the lazy
