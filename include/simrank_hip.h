@@ -494,6 +494,9 @@ SIMRANK_API int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* up
  * What leg 1 of the LATEST update left out (simrank_plan only; tuning "leg1_skip"):
  *      "leg1_units"      workgroups of the one-launch leg 1 that own a unit (0: the launch was another kernel)
  *      "leg1_skipped"    how many of them returned at once: their tiles of the transposed product are read by nobody
+ * What leg 2 of the LATEST update took (tuning "leg2_short"):
+ *      "leg2_short_groups"  groups of four 32-row tiles whose workgroups ran the short path of the upper-triangle gather
+ *                        leg 2 (0: the knob is off, no group is short, or the launch was another kernel or instantiation)
  * simrank_biplan_get answers the same keys per group (layout 0).  simrank_shardplan_get answers them for the rank's
  * column block: layout 1 (f32 row-major, "iterate_stride" = ld) or 2 (fp16-held, "iterate_stride" = rows_pad), n rows,
  * columns [col_lo, col_hi) of the solver's order; the block's column ids are "ids" + col_lo (the same values as
@@ -717,6 +720,13 @@ SIMRANK_API int simrank_shardbiplan_destroy(simrank_shardbiplan* bp);
  *      "leg1_order" the one-matrix plan's node order: 1 rows of equal length in the order of their first referencing row
  *                 (what makes such units common), 0 the stable length order of the sharded plans (the same bits as their
  *                 loops), -1 (default) the former from 16384 nodes on, where a fit repays the extra sorts
+ *      "leg2_short" 0, 8 or 16 (default 16): workgroups of the upper-triangle gather leg 2 whose four tiles are whole 32-row
+ *                 blocks with at most this many entries per row read a padded image of their ids, lengths and scales
+ *                 (built with the graph) instead of the row pointers and the id stream, and request the previous iterate
+ *                 of all their rows at once; the same bits as 0.  Only with 16-bit ids, 32-bit operand addressing and
+ *                 panel-blocked operands, unrestricted, without a dense part; every other launch, and every launch on a
+ *                 graph without a short group, runs the kernel it ran without the path.  Read when the graph (or the
+ *                 plan that owns it) is created: setting it afterwards does not change an existing graph
  *      "dense_sym" dense part in the upper-triangle form of leg 2: 1 always, 0 never, -1 when
  *                 the dense sets hold at least half of the entries
  *      "sym_desc" 0/1  upper-triangle leg 2: an XCD takes its panels in descending order (default 1)

@@ -116,6 +116,57 @@ int64_t build_tiles(const int32_t* rowptr, int64_t n_rows, int64_t nnz, int64_t 
     return n_tiles;
 }
 
+// ---- the padded id image of leg 2's short workgroups (common.h ShortImage)
+void build_short_image(const int32_t* rowptr, const int32_t* col, const float* rowscale, int64_t n_rows,
+                       const std::vector<int32_t>& tile_row0, int64_t n_tiles, int32_t width, ShortImage& out) {
+    out = ShortImage();
+    if ((width != 8 && width != 16) || n_tiles <= 0 || n_rows < 64) return;
+    const int64_t groups = (n_tiles + 3) / 4;
+    out.is_short.assign((size_t)groups, 0);
+    for (int64_t k = 0; k < groups; ++k) {
+        bool ok = true;
+        for (int64_t t = 4 * k; ok && t < std::min<int64_t>(4 * k + 4, n_tiles); ++t) {
+            const int64_t lo = tile_row0[(size_t)t], hi = tile_row0[(size_t)t + 1];
+            ok = lo % 32 == 0 && hi == std::min<int64_t>(n_rows, lo + 32);
+            for (int64_t a = lo; ok && a < hi; ++a) ok = rowptr[a + 1] - rowptr[a] <= width;
+        }
+        out.is_short[(size_t)k] = ok ? 1 : 0;
+        out.groups += ok ? 1 : 0;
+    }
+    if (out.groups == 0) return;
+    out.width = width;
+    const size_t tiles_pad = (size_t)groups * 4;
+    out.tiles.assign(tiles_pad * 2, 0);
+    out.meta.assign(tiles_pad * 8 * 8, 0u);
+    out.ids.assign(tiles_pad * 64 * (size_t)(width / 2), (uint16_t)0xFFFF);
+    const int nc = width / 8;
+    for (int64_t t = 0; t < n_tiles; ++t) {
+        if (!out.is_short[(size_t)(t / 4)]) continue;
+        const int32_t lo = tile_row0[(size_t)t];
+        const int nrows = tile_row0[(size_t)t + 1] - lo;
+        out.tiles[2 * (size_t)t] = lo;
+        out.tiles[2 * (size_t)t + 1] = nrows;
+        int order[32];
+        for (int r = 0; r < nrows; ++r) order[r] = r;
+        std::sort(order, order + nrows, [&](int x, int y) {
+            const int32_t lx = rowptr[lo + x + 1] - rowptr[lo + x], ly = rowptr[lo + y + 1] - rowptr[lo + y];
+            return lx != ly ? lx > ly : x > y;
+        });
+        for (int s = 0; s < nrows; ++s) {
+            const int r = order[s], ps = s / 8, g = s % 8;
+            const int32_t start = rowptr[lo + r], len = rowptr[lo + r + 1] - start;
+            uint32_t* m = out.meta.data() + ((size_t)t * 8 + (size_t)g) * 8;
+            std::memcpy(m + ps, rowscale + lo + r, 4);
+            m[4] |= (uint32_t)len << (8 * ps);
+            m[5] |= (uint32_t)r << (8 * ps);
+            for (int32_t j = 0; j < len; ++j) {
+                const int lane = 8 * g + (j & 7), c = j >> 3;
+                out.ids[((size_t)t * 64 + (size_t)lane) * (size_t)(width / 2) + (size_t)(ps * nc + c)] = (uint16_t)col[start + j];
+            }
+        }
+    }
+}
+
 // ---- device block pool.  hipMalloc maps a 17 GiB matrix in 0.4-0.5 s on some boxes (1.6-2.0 s of a config-5
 // set-up against 0.12 s for its four updates: profiles/r03_setup_before_pool.log), so blocks of at least
 // kPoolMin bytes are kept when their owner lets go of them and handed to the next request they fit (smallest
@@ -797,6 +848,21 @@ int graph_create_with(const Tuning& tun, int64_t n_rows, int64_t n_cols, int64_t
     if (!rc && g->ev_hubs) rc = up((void**)&g->ev_hubidx, hubidx.data(), size_t(n_cols) * 4);
     if (!rc && g->n_tiles) rc = up((void**)&g->tile_row0, tile_row0.data(), tile_row0.size() * 4);
     if (!rc && g->sym_blocks) rc = up((void**)&g->sym_map, sym_map.data(), sym_map.size() * 4);
+    if (!rc && g->sym_blocks && g->col16 && g->tun.leg2_short > 0) {
+        // (16-bit ids only: the image holds nothing else; which launch reads it: spmm.hip launch_gather3)
+        ShortImage img;
+        build_short_image(rowptr, col, rowscale, n_rows, tile_row0, g->n_tiles, (int32_t)g->tun.leg2_short, img);
+        if (img.groups > 0) {
+            for (size_t k = 0; k < sym_map.size() / 2; ++k)
+                if (sym_map[2 * k] >= 0 && img.is_short[(size_t)sym_map[2 * k + 1]]) sym_map[2 * k + 1] |= 1 << 30;
+            g->short_w = img.width;
+            g->short_groups = img.groups;
+            rc = up((void**)&g->sym_map_short, sym_map.data(), sym_map.size() * 4);
+            if (!rc) rc = up((void**)&g->short_tiles, img.tiles.data(), img.tiles.size() * 4);
+            if (!rc) rc = up((void**)&g->short_meta, img.meta.data(), img.meta.size() * 4);
+            if (!rc) rc = up((void**)&g->short_ids, img.ids.data(), img.ids.size() * 2);
+        }
+    }
     if (!rc && after_base && *after_base) rc = (*after_base)(g);     // (the builders are still at work on their threads)
     const double t_base = since();
     for (int i = 0; i < n_jobs; ++i) {
@@ -845,6 +911,10 @@ int simrank_graph_destroy(simrank_graph* g) {
 #endif
     plan_free(g->tile_row0);
     plan_free(g->sym_map);
+    plan_free(g->sym_map_short);
+    plan_free(g->short_ids);
+    plan_free(g->short_meta);
+    plan_free(g->short_tiles);
     free_dense_plan(g->dense);
     free_fused_plan(g->fused);
 #ifdef SIMRANK_EXPERIMENT_FUSED2
@@ -987,6 +1057,9 @@ int simrank_set_tuning(const char* key, int64_t value) {
     } else if (!strcmp(key, "leg1_order")) {
         SR_REQUIRE(value >= -1 && value <= 1, "leg1_order must be -1 (by the graph's size), 0 or 1");
         t.leg1_order = value;
+    } else if (!strcmp(key, "leg2_short")) {
+        SR_REQUIRE(value == 0 || value == 8 || value == 16, "leg2_short must be 0 (off), 8 or 16");
+        t.leg2_short = value;
     } else {
         SR_REQUIRE(false, "unknown tuning key '%s'", key);
     }
@@ -1034,6 +1107,7 @@ int simrank_get_tuning(const char* key, int64_t* value) {
     else if (!strcmp(key, "restrict_support")) *value = t.restrict_support;
     else if (!strcmp(key, "leg1_skip")) *value = t.leg1_skip;
     else if (!strcmp(key, "leg1_order")) *value = t.leg1_order;
+    else if (!strcmp(key, "leg2_short")) *value = t.leg2_short;
     else SR_REQUIRE(false, "unknown tuning key '%s'", key);
     return SIMRANK_OK;
 }

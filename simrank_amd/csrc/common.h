@@ -59,6 +59,11 @@ struct Tuning {
                              // the one-launch plan's dcols / sids streams); 0: 32-bit ids at any size
     int64_t sym_desc = 1;    // upper-triangle leg 2: an XCD takes its panels in descending order — the big ones (N/128
                              // workgroups: one panel at a time in its L2) first, the small ones as the tail: leg 2 -4.7 %
+    int64_t leg2_short = 16; // upper-triangle leg 2: workgroups whose tiles are whole and whose rows have at most this many entries
+                             // (8 or 16) read a padded id image and run without the rowptr -> ids chain, the previous iterate of
+                             // all their rows requested before the first gather (spmm.hip short_group3); 0 = off.  Read when
+                             // a graph is created (the image is built there); launches without short groups run the kernel
+                             // they ran without the path
     int64_t ev_tri = 1;      // evidence counts of a whole square block: paths to b >= a only + a mirror pass (round 4)
     int64_t ev_hub = 14;     // ... columns with at least this many thousandths of n_rows live rows (and >= 48) are counted on the
                              // matrix cores (i8 product of their 0/1 image), the rest on the LDS counters (round 5); 0 = off
@@ -366,6 +371,25 @@ int launch_dense_tiles(const simrank_graph* g, const float* X, int64_t ldx, int6
 // ceil(n_tiles / 4) workgroup groups (most entries first)
 int64_t build_tiles(const int32_t* rowptr, int64_t n_rows, int64_t nnz, int64_t balance,
                     std::vector<int32_t>& tile_row0, std::vector<int32_t>& sym_map, bool sym_descending);
+// The padded id image of leg 2's SHORT workgroups (api.hip; read by spmm.hip short_group3).  Group k = tiles 4 k .. 4 k + 3
+// of build_tiles' list is short when each of its tiles is a whole 32-row block (or the ragged last one) and none of its rows
+// has more than `width` (8 or 16) entries.  Per tile t (every array covers 4 * ceil(n_tiles / 4) tiles; those of other
+// groups stay zero and are never read), rows in the kernel's longest-first order (length descending, then row descending),
+// sorted row s = pass s / 8, lane group s % 8:
+//   tiles[2 t], [2 t + 1]   first row, rows
+//   meta[(8 t + g) * 8 ..]  the four passes' row scales (float bits), then lengths and row indices inside the tile (one byte
+//                           per pass each), two spare words
+//   ids[(64 t + lane) * width / 2 + pass * width / 8 + c]   entry 8 c + (lane & 7) of the row of lane group lane >> 3 in
+//                           that pass; 0xFFFF where the row has none (the kernel puts the launch's out-of-range id there)
+struct ShortImage {
+    int32_t width = 0, groups = 0;
+    std::vector<uint8_t> is_short;      // per group
+    std::vector<int32_t> tiles;
+    std::vector<uint32_t> meta;
+    std::vector<uint16_t> ids;
+};
+void build_short_image(const int32_t* rowptr, const int32_t* col, const float* rowscale, int64_t n_rows,
+                       const std::vector<int32_t>& tile_row0, int64_t n_tiles, int32_t width, ShortImage& out);
 }
 
 // The graph object: device CSR of the 0/1 pattern + per-row scale, and the transposed
@@ -392,6 +416,15 @@ struct simrank_graph {
     int32_t n_tiles = 0;
     int32_t* sym_map = nullptr;
     int32_t sym_blocks = 0;
+    // the short workgroups of that list (tuning "leg2_short"; simrank::ShortImage): the list with their entries flagged,
+    // and the padded id image; all NULL / 0 when the knob is off or no workgroup is short
+    int32_t* sym_map_short = nullptr;
+    uint32_t* short_ids = nullptr;
+    uint32_t* short_meta = nullptr;
+    int32_t* short_tiles = nullptr;
+    int32_t short_w = 0, short_groups = 0;
+    mutable int32_t leg2_short_taken = 0;  // short groups of the latest epilogue launch ON THIS GRAPH; a plan owns its graph and
+                                           // copies it behind its leg 2 (side_t::leg2_short_groups, plan key "leg2_short_groups")
     simrank_dense_plan* dense = nullptr;   // NULL: no block of the pattern is dense enough
     simrank_fused_plan* fused = nullptr;   // leg 1 as one launch (fused.hip); NULL: tuning "fuse" = 0
     std::atomic<int> fused_build{0};       // its builder thread during simrank_graph_create: 0 none, 1 running, 2 finished (the

@@ -45,6 +45,7 @@ struct side_t {
     std::vector<int32_t> first_block_host;
     int64_t leg1_units = 0, leg1_skipped = 0;  // of the latest update: workgroups of the one-launch leg 1 that have a unit, and
                                                // how many of them returned at once ("leg1_units", "leg1_skipped")
+    int64_t leg2_short_groups = 0;             // of the latest update: short groups its leg 2 took ("leg2_short_groups")
     int64_t dead_units = -1;                   // what the table skips of such a launch (-1: not counted yet)
 };
 
@@ -212,6 +213,8 @@ int side_leg_pair(side_t& a, const side_t& o, bool from_identity, bool asym, dou
         rc = a.half ? simrank_spmm_blocked_h16(a.g, a.Tt, a.k_rows_pad, a.n, a.S[nx], a.rows_pad, 0, &ep, a.rows_pad, kHalfScale, st)
                     : simrank_spmm_blocked(a.g, a.Tt, a.k_rows_pad, a.n, a.S[nx], a.rows_pad, 0, &ep, st);
     }
+    // (the launch's answer, copied while this update is the graph's latest launch: the side owns its graph)
+    a.leg2_short_groups = (asym || a.half || rc) ? 0 : a.g->leg2_short_taken;
     if (!rc) rc = stamp();
     if (rc) return rc;
     SR_HIP(hipMemcpyAsync(host_slot, counters, sizeof(unsigned long long) * SIMRANK_CHANGED_SLOTS, hipMemcpyDeviceToHost, st));
@@ -321,6 +324,7 @@ inline int side_get(const side_t& a, const char* key, int64_t* value) {
     else if (!strcmp(key, "ids")) *value = (int64_t)(uintptr_t)a.ord_dev;
     else if (!strcmp(key, "leg1_units")) *value = a.leg1_units;
     else if (!strcmp(key, "leg1_skipped")) *value = a.leg1_skipped;
+    else if (!strcmp(key, "leg2_short_groups")) *value = a.leg2_short_groups;
     else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }

@@ -84,6 +84,14 @@ struct SpmmArgs {
     int32_t n_tiles;
     const int32_t* sym_map;   // kSym + tile list: blockIdx -> (panel, workgroup of the panel) pairs
     int32_t sym_blocks;
+    // short workgroups of that list (tuning "leg2_short"; common.h ShortImage): the same list with kShortFlag on their
+    // entries, and the padded id image their waves read instead of rowptr / rowscale / col16; NULL = none
+    const int32_t* sym_map_short;
+    const uint32_t* short_ids;    // [tile][lane][pass][chunk] 16-bit ids, W bytes per lane
+    const uint32_t* short_meta;   // [tile][lane group][8 words]: four row scales, lengths, rows, two spare
+    const int32_t* short_tiles;   // [tile][2]: first row, rows
+    int32_t short_w;              // W: 8 or 16
+    int32_t short_groups;
     int32_t xcd_map;
     int32_t has_ep;
     // epilogue (has_ep)
@@ -884,6 +892,114 @@ __device__ __forceinline__ void emit_row3(const SpmmArgs& p, float* tbuf_wave, i
     }
 }
 
+// ---- the short path of the upper-triangle leg (tuning "leg2_short" = W; the image: api.hip build_short_image).
+// A workgroup whose four tiles are whole and whose rows have at most W entries reads, per wave, ONE record per lane
+// addressed from its map entry: the ids of its slots in all four passes (rows already in the kernel's longest-first
+// order, padded to W), the rows' lengths, indices and scales.  No rowptr -> ids chain, no sort, no phases A0 / A, no
+// workgroup barrier (the LDS tile is the wave's own).  The previous iterate of all four passes is requested beside the
+// image, before any gather.
+// Per row the sum is phase B's: slots 0 .. (longest row of the pass) - 1 in order into a zero accumulator, slots the
+// row does not have carry the out-of-range id and load zeros; emit_row3 is the same call.  Same bits.
+constexpr int kShortFlag = 1 << 30;
+
+__device__ __forceinline__ void short_group3(const SpmmArgs& p, const Src32& xs, float* tbuf_wave, int t, int panel, int lane,
+                                             int64_t c0, int64_t mycol, int64_t colofs, bool col_active, bool check_prev,
+                                             unsigned& changed) {
+    constexpr int RT = 32, PW = 32;
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    const int g = lane >> 3, q = lane & 7, gbase = lane & ~7;
+    const int nc = p.short_w >> 3;                              // chunks of 8 ids per row: 1 or 2
+    const int row0 = p.short_tiles[2 * t];                      // (uniform address: scalar loads)
+    int nrows = p.short_tiles[2 * t + 1];
+    const uint32_t* idp = p.short_ids + (size_t(t) * 64 + lane) * size_t(2 * nc);
+    v4u idw = {0u, 0u, 0u, 0u};
+    if (nc == 2) {
+        idw = *reinterpret_cast<const v4u*>(idp);
+    } else {
+        const v2u w = *reinterpret_cast<const v2u*>(idp);
+        idw.x = w.x;
+        idw.y = w.y;
+    }
+    const uint32_t* meta = p.short_meta + (size_t(t) * 8 + g) * 8;
+    const f4 scales = *reinterpret_cast<const f4*>(meta);
+    const v2u lr = *reinterpret_cast<const v2u*>(meta + 4);      // lengths, rows: a byte per pass
+    if (row0 > c0) nrows = 0;                                   // (whole tiles: row0 is the tile's 32-row block)
+    const bool mirror = row0 < c0;
+    if (nrows == 0) return;
+
+    // The previous iterate of all four passes' rows, requested beside the image, before any gather: buffer loads through a
+    // descriptor over the panel (nothing to compare with — no previous iterate, or count_any with a difference known:
+    // zero bytes, no access).
+    const __amdgpu_buffer_rsrc_t prd = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(check_prev ? p.prev + int64_t(panel) * p.y_rows_pad * 32 : p.prev), 0,
+        check_prev ? int(p.y_rows_pad * 128) : 0, 0x00020000);
+    float old[4][4];
+#pragma unroll
+    for (int ps = 0; ps < 4; ++ps) {
+        const int r = int((lr.y >> (8 * ps)) & 255u);          // (a lane group without a row in the pass: the tile's first row)
+        const v4u w = __builtin_amdgcn_raw_buffer_load_b128(prd, (row0 + r) * 128 + q * 16, 0, 2);     // (2: non-temporal)
+        old[ps][0] = __uint_as_float(w.x); old[ps][1] = __uint_as_float(w.y);
+        old[ps][2] = __uint_as_float(w.z); old[ps][3] = __uint_as_float(w.w);
+    }
+    const float dsum[4] = {0.f, 0.f, 0.f, 0.f};
+    // One pass: a chunk of 8 slots as phase B gathers it, four gathers in flight at a time (gather_chunk).  Measured at the
+    // compiler: eight in flight, or the next pass's first four across emit_row3, spill beside the early loads at six waves
+    // per SIMD (profiles/leg2_short_ab.md).
+    auto pass = [&](int ps, const float (&old_ps)[4], float sc) {
+        if (8 * ps >= nrows) return;
+        const int len = int((lr.x >> (8 * ps)) & 255u);
+        const int r = int((lr.y >> (8 * ps)) & 255u);
+        const int n = (p.probe & 1) ? 0 : __builtin_amdgcn_readfirstlane(len);      // the longest row's: lane group 0 holds it
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int k = 0; k < n; k += 8) {
+            // this lane's id of chunk k / 8: entry k + q of the row of lane group g
+            const int h = ps * nc + (k >> 3);                       // (uniform) half-word h of the lane's record
+            const unsigned w01 = (h & 2) ? idw.y : idw.x, w23 = (h & 2) ? idw.w : idw.z;
+            const int raw = int((((h & 4) ? w23 : w01) >> (16 * (h & 1))) & 0xFFFFu);
+            const int iv = (k + q < len && !(p.probe & 8)) ? (raw & p.idx_mask) : xs.sent();
+            gather_chunk<1>(xs, iv, gbase, min(8, n - k), 0, 0, acc);      // (range-checked source: every add unmasked)
+        }
+        if (8 * ps + g < nrows && col_active)
+            emit_row3<kSym>(p, tbuf_wave, r, int64_t(row0) + r, q, mycol, colofs, sc, acc, dsum, changed, mirror, check_prev, old_ps);
+    };
+    pass(0, old[0], scales.x);
+    pass(1, old[1], scales.y);
+    pass(2, old[2], scales.z);
+    pass(3, old[3], scales.w);
+
+    // the mirrored tile (panel-blocked Y^T), as in the general path; the LDS tile is this wave's alone
+    if (mirror && !(p.probe & 2)) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const int cols_here = int(imin(PW, p.L - c0));
+        float* base = p.Y + ((int64_t(row0 >> 5) * p.y_rows_pad) + c0) * 32;
+        if (cols_here == PW && (nrows & 3) == 0) {
+#pragma unroll
+            for (int it = 0; it < PW * (RT / 4) / 64; ++it) {
+                const int x = lane + it * 64;
+                const int c = x >> 3;
+                const int r4 = (x & 7) * 4;
+                if (r4 < nrows) {
+                    const float* tb = tbuf_wave + c * (RT + 1) + r4;
+                    const float v4[4] = {tb[0], tb[1], tb[2], tb[3]};
+                    float* dst = base + c * 32 + r4;
+                    if (p.nt) vstore_nt<4>(dst, v4); else vstore<4>(dst, v4);
+                }
+            }
+        } else {
+            for (int x = lane; x < PW * RT; x += 64) {
+                const int c = x >> 5;
+                const int r = x & 31;
+                if (c < cols_here && r < nrows) base[c * 32 + r] = tbuf_wave[c * (RT + 1) + r];
+            }
+        }
+    }
+}
+
 // RESTRICT (leg 2 of SimRank++, SimRank.py:315-316, :361): a separate instantiation, so the plain
 // legs keep their register budget; chosen by the driver when few segments of E are live.
 #ifdef SIMRANK_STAMPS
@@ -914,7 +1030,9 @@ __device__ __forceinline__ unsigned long long stamp_now() {
 // registers of those sums: 60 instead of 68 VGPRs for the transposed leg (8 waves per SIMD), 79
 // instead of 89 for the others (6 instead of 5): leg 2 -5...7 %.
 // A32: Src32 addressing (see above).
-template <int MODE, bool IDS16, bool RESTRICT, bool DENSE, bool A32>
+// SHORT: the launch list flags short workgroups (short_group3); only <kSym, IDS16, !RESTRICT, !DENSE, A32> has that
+// form, and only launches that have short groups run it — every other launch runs the code it ran without the path.
+template <int MODE, bool IDS16, bool RESTRICT, bool DENSE, bool A32, bool SHORT = false>
 #ifndef SIMRANK_LB_DELTA
 #define SIMRANK_LB_DELTA 0      // experiment builds lower the occupancy bounds by this much
 #endif
@@ -1020,6 +1138,21 @@ void gather3_kernel(const SpmmArgs p) {
                 const_cast<unsigned long long*>(p.n_changed), 0, watch ? SIMRANK_CHANGED_SLOTS * 8 : 0, 0x00020000);
             const v2u w = __builtin_amdgcn_raw_buffer_load_b64(csrd, int(slot * 8u), 0, 16);
             seen = (unsigned long long)w.x | ((unsigned long long)w.y << 32);
+        }
+    }
+
+    if constexpr (SHORT) {
+        if (rt & kShortFlag) {      // (workgroup-uniform; set only in the list of a launch that has the image)
+            const bool cp = p.has_ep && p.prev && __builtin_amdgcn_readfirstlane(int(seen != 0)) == 0;
+            const int t = (rt & ~kShortFlag) * kWaves + wave;
+            short_group3(p, xs, tbuf_wave, t, panel, lane, c0, mycol, colofs, col_active, cp, changed);
+            STAMP(3);               // (all of a short wave counts as phase B)
+            if (p.has_ep && p.prev) {
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) changed += __shfl_down(changed, off);
+                if (lane == 0 && changed) atomicAdd(p.n_changed + slot, (unsigned long long)changed);
+            }
+            return;
         }
     }
 
@@ -1367,7 +1500,7 @@ void gather3_kernel(const SpmmArgs p) {
 }
 
 template <int MODE>
-static int launch_gather3(SpmmArgs a, hipStream_t st) {
+static int launch_gather3(SpmmArgs a, hipStream_t st, int32_t* short_taken = nullptr) {
     constexpr int PW = 32, RT = 32;
     a.n_panels = int((a.L + PW - 1) / PW);
     if (MODE == kShard && a.sh_ntiles > 0) a.n_panels = a.sh_ntiles;     // one stage of the leg
@@ -1395,6 +1528,20 @@ static int launch_gather3(SpmmArgs a, hipStream_t st) {
                      a.ldx * 4 < (int64_t(1) << 24) && x_rows < (int64_t(1) << 24) - 1;
     a.x_span_bytes = span;
     a.x_sentinel = (int32_t)x_rows;
+    // the short path lives in ONE instantiation (kSym, 16-bit ids, 32-bit addressing, unrestricted, no dense part; SHORT)
+    // and stores its mirrored tile panel-blocked: any other launch walks the plain list in the kernel it always ran
+    const bool take_short = MODE == kSym && a.sym_map_short && a.short_groups > 0 && a.tile_row0 && a32 && a.col16 &&
+                            !restricted && !dense && a.blocked;
+    if (!take_short) a.short_groups = 0;
+    if (short_taken) *short_taken = a.short_groups;
+    if constexpr (MODE == kSym) {
+        if (take_short) {
+            a.sym_map = a.sym_map_short;
+            hipLaunchKernelGGL((gather3_kernel<kSym, true, false, false, true, true>), gr, bl, lds, st, a);
+            SR_HIP(hipGetLastError());
+            return SIMRANK_OK;
+        }
+    }
 #define SR_LAUNCH3(IDS, RES, DEN) \
     do { if (a32) hipLaunchKernelGGL((gather3_kernel<MODE, IDS, RES, DEN, true>), gr, bl, lds, st, a); \
          else hipLaunchKernelGGL((gather3_kernel<MODE, IDS, RES, DEN, false>), gr, bl, lds, st, a); } while (0)
@@ -2128,6 +2275,7 @@ static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_
     if (!transpose_out) vec_ok = vec_ok && aligned16(Y) && ldy % 4 == 0;
     hipStream_t st = as_stream(stream);
     if (ep) {
+        if (!(sk && sk->dry)) g->leg2_short_taken = 0;      // (the launch below that takes the short path says so)
         a.has_ep = 1;
         a.coef = ep->coef;
         a.lbd = ep->lbd;
@@ -2225,6 +2373,14 @@ static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_
             a.n_tiles = dp ? dp->r_n_tiles : g->n_tiles;
             a.sym_map = dp ? dp->r_sym_map : g->sym_map;
             a.sym_blocks = dp ? dp->r_sym_blocks : g->sym_blocks;
+            if (!dp && g->sym_map_short) {
+                a.sym_map_short = g->sym_map_short;
+                a.short_ids = g->short_ids;
+                a.short_meta = g->short_meta;
+                a.short_tiles = g->short_tiles;
+                a.short_w = g->short_w;
+                a.short_groups = g->short_groups;
+            }
         }
     }
     if (!vec_ok) {
@@ -2239,7 +2395,7 @@ static int spmm_impl(const simrank_graph* g, const float* X, int64_t ldx, int64_
     if (blocked) {
         SR_REQUIRE(lean_ok && (T.panel == 0 || T.panel == 32),
                    "panel-blocked operands need the lean kernel (tile 32, panel 32, < 2^24 rows)");
-        if (want_sym) return launch_gather3<kSym>(a, st);
+        if (want_sym) return launch_gather3<kSym>(a, st, &g->leg2_short_taken);
         return transpose_out ? launch_gather3<kTrans>(a, st) : launch_gather3<kPlain>(a, st);
     }
     if (lean_ok && want_sym) {
