@@ -689,6 +689,80 @@ class _KeptModel:
         _, _, labels = self._kept(group)
         return pd.Series(_linkage.cut_labels(len(labels), Z, t, k), index=pd.Index(labels), name="component", dtype=np.int64)
 
+    def _cluster_scores(self, labels, group, want_means=False, max_bytes=None):
+        """What the four methods below share: the checked labelling, then the sweep.  -> (the frame's pandas Index,
+        clusters int64 [K] ascending, every node's cluster rank, the sizes, own, other, nearest rank or -1, means)."""
+        from . import _groups
+        solver, j, lab = self._kept(group)
+        index, _ = self._ids(j, lab, [])
+        clusters, gidx, sizes = _groups.groups_of(_groups.check_labels(labels, index))
+        if max_bytes is not None:
+            _groups.check_means_bytes(len(index), clusters.size, max_bytes)
+        if len(index) == 0:
+            empty = np.empty(0, dtype=np.float64)
+            return index, clusters, gidx, sizes, empty, empty, np.empty(0, dtype=np.int64), np.empty((0, 0))
+        return (index, clusters, gidx, sizes) + tuple(_groups.scores(solver, j, gidx, sizes, want_means))
+
+    def cluster_quality(self, labels, group=None):
+        """A clustering scored node by node.  ``labels``: the cluster of every fitted node, as ``cut``, ``components(t)``
+        or anything else gives it: a pandas Series indexed by the fitted labels (any order; every node exactly once) or a
+        1-D sequence of length N in the dense frame's order; values are integers of any sign (bool, floats, NaN and None
+        are a ValueError), a cluster is one distinct value.  A bad argument is a ValueError (a KeyError for an unknown
+        label) before any device work.  ``group=1 | 2`` for the bipartite classes.
+
+        For node a and cluster g, ``M_g(a) = {b : labels[b] = g, b != a}``; ``sum(a, g)`` adds ``S[a, b]`` over it in
+        float64 (row a, the element ``similarity(a, b)`` reads: the matrices are not symmetric in general; every element
+        widened as ``rows`` widens it); ``mean(a, g) = sum / |M_g(a)|``, NaN when the set is empty.  A NaN entry makes its
+        (node, cluster) mean NaN; -0.0 counts as zero.
+
+        -> DataFrame, one row per node, index = the dense frame's labels in its order:
+        ``cluster`` (int64) the node's; ``own`` (float64) = ``mean(a, labels[a])``, NaN for a singleton; ``other`` the
+        best ``mean(a, g)`` over g != labels[a] and ``nearest`` (int64) that cluster, in the order (mean descending,
+        cluster value ascending), a NaN mean never chosen; with no candidate ``nearest = labels[a]`` and ``other`` = NaN;
+        ``silhouette``, checked in this order: 0.0 for a singleton, NaN if ``own`` or ``other`` is NaN, otherwise
+        ``(own - other) / max(own, other)`` when that maximum is > 0, else 0.0.
+
+        One sweep of the iterate in place on the device (libsimrank_groups.so), three numbers per node cross.  The order
+        of a sum's additions depends on the layout, the shape and the labelling alone and there are no floating-point
+        atomics: two runs give the same bits, and ``|sum - exact| <= m * 2^-52 * sum |S[a, b]|`` over the ``m`` members.
+        A model held in several column blocks (``LocalWorld(P)``) is packed into one temporary block first, as ``prune``
+        does.  A pruned model is answered on the host from its lists for its matrix P, whose absent entries are +0.0:
+        they count in ``|M_g(a)|`` and add nothing.  The model is left unchanged."""
+        from . import _groups
+        index, clusters, gidx, sizes, own, other, nearest, _ = self._cluster_scores(labels, group)
+        near = np.where(nearest >= 0, clusters[np.maximum(nearest, 0)], clusters[gidx]) if len(index) else nearest
+        return pd.DataFrame({"cluster": clusters[gidx], "own": own, "nearest": near.astype(np.int64), "other": other,
+                             "silhouette": _groups.silhouette(own, other, sizes[gidx])}, index=index.copy())
+
+    def cluster_means(self, labels, group=None, max_bytes=2 ** 30):
+        """DataFrame [N x K] float64: ``mean(a, g)`` of ``cluster_quality`` for every node (index: the dense frame's
+        labels) and every cluster (columns: the cluster values, ascending).  An answer of ``N * K * 8`` bytes above
+        ``max_bytes`` is a ValueError before any transfer."""
+        from . import _groups
+        index, clusters, _, _, _, _, _, means = self._cluster_scores(labels, group, True, _groups.check_max_bytes(max_bytes))
+        return pd.DataFrame(means, index=index.copy(), columns=pd.Index(clusters, name="cluster"))
+
+    def medoids(self, labels, group=None):
+        """Series "medoid": cluster -> the label of its medoid, index = the clusters ascending.  The medoid is the member
+        with the largest ``own`` of ``cluster_quality``; ties go to the first member in the frame's order, NaN is skipped;
+        if every member's ``own`` is NaN (a singleton), the first member."""
+        from . import _groups
+        index, clusters, gidx, _, own, _, _, _ = self._cluster_scores(labels, group)
+        at = _groups.medoid_positions(gidx, clusters.size, own)
+        return pd.Series(index.take(at).to_numpy(), index=pd.Index(clusters, name="cluster"), name="medoid")
+
+    def cluster_summary(self, labels, group=None):
+        """DataFrame, one row per cluster (index: the clusters ascending): ``size`` (int64), ``medoid`` (as ``medoids``),
+        and ``cohesion``, ``separation``, ``silhouette``: ``math.fsum(...) / size`` of the members' ``own``, ``other`` and
+        ``silhouette`` of ``cluster_quality``; NaN propagates (a singleton's cohesion is NaN).  Host arithmetic."""
+        from . import _groups
+        index, clusters, gidx, sizes, own, other, _, _ = self._cluster_scores(labels, group)
+        sil = _groups.silhouette(own, other, sizes[gidx])
+        at = _groups.medoid_positions(gidx, clusters.size, own)
+        cohesion, separation, mean_sil = _groups.summary(gidx, clusters.size, own, other, sil)
+        return pd.DataFrame({"size": sizes, "medoid": index.take(at).to_numpy(), "cohesion": cohesion,
+                             "separation": separation, "silhouette": mean_sil}, index=pd.Index(clusters, name="cluster"))
+
     def compact(self, precision=None):
         """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense
         frame's order (libsimrank_model.so), then the plan's matrices are released (the evidence counts stay, so the lazy
