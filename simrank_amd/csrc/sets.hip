@@ -248,18 +248,6 @@ int64_t grid_blocks(int64_t n_sets, int64_t n_out, int32_t grid_order) {
     return 8 * ((n_sets + fewest - 1) / fewest);
 }
 
-// Whether every quad of 4 columns that lies inside the block is one aligned vector load: panels always are (32 and 64
-// divide by 4, a panel row is 128 bytes); a row-major block when its rows start on 16 (f32) or 16 (float64) bytes.
-bool vector_loads(const void* S, int32_t layout, int64_t stride) {
-    const uintptr_t p = reinterpret_cast<uintptr_t>(S);
-    switch (layout) {
-        case PANEL_F32: return p % 16 == 0;
-        case PANEL_F16: return p % 8 == 0;
-        case ROWMAJOR_F32: return p % 16 == 0 && stride % 4 == 0;
-        default: return p % 16 == 0 && stride % 2 == 0;
-    }
-}
-
 template <int L>
 void launch_score(bool vec, dim3 grid, hipStream_t st, const void* S, int64_t stride, int64_t n_rows, int64_t n_cols,
                   const int32_t* col_pos, int64_t n_out, const int64_t* set_ptr, const int32_t* set_pos,
@@ -304,7 +292,7 @@ int simrank_sets_score(const void* S, int32_t layout, int64_t stride, int64_t n_
     REQUIRE(set_ptr && out, "set_ptr or out is NULL");
     // (set_pos and set_w may be NULL when every basket is empty: they are then never read)
     const int64_t chunks = (n_out + kChunk - 1) / kChunk;
-    const bool vec = !col_pos && vector_loads(S, layout, stride);
+    const bool vec = !col_pos && quad_vector_loads(S, layout, stride);
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)blocks);
     with_layout(layout, [&](auto L) {

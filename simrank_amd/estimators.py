@@ -763,6 +763,80 @@ class _KeptModel:
         return pd.DataFrame({"size": sizes, "medoid": index.take(at).to_numpy(), "cohesion": cohesion,
                              "separation": separation, "silhouette": mean_sil}, index=pd.Index(clusters, name="cluster"))
 
+    def _seeded(self, seeds, group):
+        """What ``assign`` and ``kmedoids`` share: the model and the checked seeds -> (solver, side, the frame's pandas
+        Index, the seeds' positions in it)."""
+        from . import _kmedoids
+        solver, j, lab = self._kept(group)
+        index, _ = self._ids(j, lab, [])
+        return solver, j, index, _kmedoids.check_seeds(seeds, index)
+
+    def assign(self, seeds, group=None):
+        """Every fitted node given to the seed whose row likes it best.  ``seeds``: a sequence of K >= 1 distinct fitted
+        labels, or a pandas Series of them (its values are taken: ``medoids(labels)`` is one); cluster j (0 .. K - 1) is
+        the j-th seed's.  An empty or repeated seed or a non-sequence is a ValueError, an unknown label a KeyError, before
+        any device work.  ``group=1 | 2`` for the bipartite classes.
+
+        ``v(j, a) = S[m_j, a]``: row m_j of the j-th seed, the element ``similarity(m_j, a)`` reads (the matrices are not
+        symmetric in general; this is the row whose mean over the members ``cluster_quality`` calls ``own(m_j)``), widened
+        as ``rows`` widens it and compared in float64.  Node a gets the first j in the order (``v(j, a)`` descending, j
+        ascending): a NaN is never chosen, -0.0 equals +0.0, a seed gets its own cluster, and a node with no candidate
+        (every value NaN) gets cluster 0.  A node no seed reaches (every value +0.0) lands in cluster 0 by the tie rule.
+
+        -> DataFrame, one row per node, index = the dense frame's labels in its order: ``cluster`` (int64), ``medoid``
+        (that seed's label) and ``similarity`` (float64) = ``v(cluster, a)``; for a seed, its stored diagonal element.
+
+        K rows of the iterate are read in place on the device (libsimrank_kmedoids.so); 12 bytes per node cross.  A model
+        held in several column blocks (``LocalWorld(P)``) is packed into one temporary block first; a pruned model is
+        answered on the host for its matrix P, whose absent entries are +0.0.  The model is left unchanged."""
+        from . import _kmedoids
+        solver, j, index, at = self._seeded(seeds, group)
+        cluster, value = _kmedoids.assign(solver, j, at)
+        return pd.DataFrame({"cluster": cluster, "medoid": index.take(at[cluster]).to_numpy(), "similarity": value},
+                            index=index.copy())
+
+    def kmedoids(self, seeds, max_iter=20, group=None):
+        """Clusters around medoids: ``assign`` alternated with the move of every cluster's medoid to its most central
+        member, until no medoid moves.  ``seeds`` as ``assign`` takes them; ``max_iter``: a positive int (bool refused: a
+        ValueError).  Iteration i = 0, 1, ...:
+
+        1. Assign.  i = 0 is ``assign(seeds)``.  From then on a node in cluster c moves to the best j* (the order of
+           ``assign``) iff ``v(j*, a) > v(c, a)``, or ``v(c, a)`` is NaN and a candidate exists; otherwise it stays.
+           Medoids stay in their clusters.  ``moved`` counts the nodes whose cluster changed (N at i = 0).
+        2. Update.  ``own(a)`` of the current labelling is ``cluster_quality``'s: the same kernel on the same lists, the
+           same bits.  Cluster j keeps its medoid unless a member has a strictly larger ``own`` (NaN is never larger; a
+           NaN incumbent loses to any non-NaN); the new medoid is the member with the largest ``own``, the first in the
+           frame's order on a tie.  ``changed`` counts the clusters whose medoid changed.
+        3. Stop when ``changed == 0`` (the next assignment would move nothing) or after ``max_iter`` iterations.
+
+        Every change raises ``F = sum of S[m(a), a] over the non-medoids a`` in exact arithmetic, so no configuration
+        repeats.
+
+        -> ``(labels, clusters, history)``: ``labels`` is the frame of ``assign`` with the loop's final clusters and
+        medoids (under the stay rule a node may sit with a tied medoid of larger j); ``clusters`` has index j and the
+        columns ``medoid`` (a label), ``size`` (int64) and ``cohesion`` (float64: the medoid's ``own``, NaN for a
+        singleton); ``history`` has one row per iteration: ``moved``, ``changed`` (int64) and ``objective`` (float64) =
+        ``math.fsum(cohesion_j * (size_j - 1))`` over the clusters of two members or more, after the update.  The last
+        ``changed`` is 0 iff the loop converged.
+
+        Per iteration one ``assign`` kernel, one sweep of ``cluster_quality`` and one pick run on the device; N int32
+        labels come to the host, which regroups them and sends the lists back, and two counters come down.  Where
+        ``assign`` runs, and as it does for ``LocalWorld(P)`` (packed once per call) and pruned models (on the host).
+        The model is left unchanged."""
+        from . import _kmedoids
+        max_iter = _kmedoids.check_max_iter(max_iter)
+        solver, j, index, at = self._seeded(seeds, group)
+        cluster, medoids, value, sizes, cohesion, history = _kmedoids.kmedoids(solver, j, at, max_iter)
+        labels = pd.DataFrame({"cluster": cluster, "medoid": index.take(medoids[cluster]).to_numpy(), "similarity": value},
+                              index=index.copy())
+        clusters = pd.DataFrame({"medoid": index.take(medoids).to_numpy(), "size": sizes.astype(np.int64),
+                                 "cohesion": np.asarray(cohesion, dtype=np.float64)},
+                                index=pd.RangeIndex(len(medoids), name="cluster"))
+        moved, changed, objective = zip(*history)
+        return labels, clusters, pd.DataFrame({"moved": np.array(moved, dtype=np.int64),
+                                               "changed": np.array(changed, dtype=np.int64),
+                                               "objective": np.array(objective, dtype=np.float64)})
+
     def compact(self, precision=None):
         """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense
         frame's order (libsimrank_model.so), then the plan's matrices are released (the evidence counts stay, so the lazy
