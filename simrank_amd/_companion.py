@@ -1,5 +1,5 @@
-"""What the ctypes bindings of the thirteen companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
-``_sets``, ``_neighbors``, ``_profile``, ``_cluster``, ``_rank``, ``_linkage``, ``_groups``, ``_kmedoids``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
+"""What the ctypes bindings of the fourteen companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
+``_sets``, ``_neighbors``, ``_profile``, ``_cluster``, ``_rank``, ``_linkage``, ``_groups``, ``_kmedoids``, ``_explain``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
 the lazy load with the version check, ``check``, and the layout codes of a block of an iterate.  A binding keeps its
 prototypes, structures and host helpers.  No CPU fallback: a missing library is an error.
 """

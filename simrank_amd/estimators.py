@@ -481,6 +481,90 @@ class _KeptModel:
         idx, val = solver.score_sets(src_j, ptr, members, w, k, excl)
         return self._best_frame("node", index.take(ids), src_index, idx, val, keep_rows=np.diff(ptr) > 0)
 
+    def explain(self, a, b, k=10, group=None, max_terms=2 ** 27):
+        """WHY are a and b similar: the update gives a pair of fitted nodes of ``group`` a sum over the pairs of their
+        neighbours (their in-neighbours for the directed classes; for the bipartite classes the group-2 neighbours of
+        group-1 nodes, read from group 2's matrix, and the other way round, as ``recommend`` reads them),
+
+            next(a, b) = F(a, b) * rowscale[a] * rowscale[b] * sum_{i in I(a)} sum_{j in I(b)} S_src[i, j]     (a != b)
+
+        with ``F = coef`` for SimRank and BipartiteSimRank and ``F = (1 - lbd) * E(a, b) * coef``, ``E = 1 - 2^-|I(a) ∩
+        I(b)|``, for the ++ and prior classes.  Every term of a pair carries the same scale, so the pairs that contribute
+        most are the largest elements of the sub-matrix ``S_src[I(a), I(b)]`` and a neighbour's part is its row or column
+        sum.  ``a``, ``b``: label sequences of equal length, repeats allowed; KeyError for an unknown label.  A ValueError,
+        before any device work, for unequal lengths, ``a[i] == b[i]`` (the update SETS the diagonal, it does not sum it),
+        ``k`` not an int in 1 .. 1024, a bad ``group``, ``group=2`` on a bipartite ``strict_reference=True`` fit (as
+        ``fold_in``), and a pair whose ``|I(a)| * |I(b)|`` exceeds ``max_terms``.
+
+        -> ``(pairs, terms, neighbors)``.  ``pairs`` has one row per pair in the order given: ``a``, ``b``,
+        ``similarity`` (the stored ``S[a, b]``: the bits ``similarity`` returns), ``terms`` (int64) = ``|I(a)| * |I(b)|``,
+        ``contributors`` (int64: the terms that are neither NaN nor a zero of either sign), ``common`` (int64) = ``|I(a) ∩
+        I(b)|``, 0 when either row scale is not > 0, ``evidence`` (float64) = ``1 - 2^-min(common, 255)`` for the classes
+        with evidence and 1.0 otherwise, ``raw`` (float64: the double sum) and ``propagated`` (float64) = ``F *
+        (rowscale[a] * (rowscale[b] * raw))``, host arithmetic in float64 in exactly that association, ``F = ((1 - lbd)
+        * evidence) * coef`` with evidence.  For the classes fitted with a prior the next update's value is ``propagated
+        + lbd * prior[a, b]``: the caller holds the prior and can add it.
+
+        ``terms`` is the long frame (pair, rank, via_a, via_b, similarity, share): ``pair`` the position in the input,
+        the k largest contributors of each pair in the total order (value descending, then ``via_a``'s position in the
+        source group's frame ascending, then ``via_b``'s); NaN and ±0.0 are never listed, so a pair with fewer than k
+        contributors gets fewer rows; ``similarity = S_src[via_a, via_b]`` widened as ``rows`` widens it, ``share =
+        similarity / raw``.  ``neighbors`` is the long frame (pair, of, neighbor, sum, share): per pair one row per
+        neighbour of a (``of = "a"``, ``sum = sum_{j in I(b)} S_src[i, j]``), then one per neighbour of b (``of = "b"``,
+        ``sum = sum_{i in I(a)} S_src[i, j]``), in the order of the side's CSR row; ``share = sum / raw``.
+
+        The sums are float64 with no floating-point atomics, in an order that depends on the two lists' lengths alone: the
+        same call gives the same bits twice, and a sum of m terms lies within ``m * 2^-52 * sum |x|`` of the exact one;
+        ``raw`` is the sum of a's marginals; NaN propagates.  The sub-matrices are gathered from the iterate in place on
+        the device (libsimrank_explain.so) in bands that fit the scratch slab; only the sums, the counts and the k best
+        cross.  A model held in several column blocks (``LocalWorld(P)``) is packed into one temporary block first; a
+        pruned model is answered on the host for its matrix P, whose absent entries are +0.0.  The model is unchanged."""
+        from . import _explain, _foldin
+        a, b = _explain.check_pairs(a, b)
+        k, max_terms = _explain.check_k(k), _explain.check_max_terms(max_terms)
+        if self._model is None:
+            self._kept(1)                                   # (raises: no kept model, or released)
+        solver, sides = self._model
+        side = _foldin.side_of(len(sides), group)
+        specs = getattr(solver, "specs", None)
+        strict = bool(specs and len(specs) == 2 and specs[1].evidence_from is not None
+                      and specs[1].evidence_from is specs[0].csr)
+        _foldin.check_strict_group(len(sides), side, strict)
+        j, labels = sides[side]
+        src_j, src_labels = sides[len(sides) - 1 - side]
+        src_index, _ = self._ids(src_j, src_labels, [])
+        index, ia = self._ids(j, labels, a)
+        _, ib = self._ids(j, labels, b)
+        same = np.flatnonzero(ia == ib)
+        if same.size:
+            raise ValueError(f"a[{int(same[0])}] == b[{int(same[0])}] == {a[int(same[0])]!r}: the update sets the diagonal "
+                             "to 1, it does not sum it; there is nothing to explain")
+        r = _explain.explain(solver, j, src_j, solver.specs[side], ia, ib, k, max_terms, labels=(a, b))
+        n = len(a)
+        pairs = pd.DataFrame({"a": index.take(ia).to_numpy() if n else np.empty(0, dtype=object),
+                              "b": index.take(ib).to_numpy() if n else np.empty(0, dtype=object),
+                              "similarity": r["similarity"], "terms": r["terms"], "contributors": r["contributors"],
+                              "common": r["common"], "evidence": r["evidence"], "raw": r["raw"],
+                              "propagated": r["propagated"]})
+        keep = r["best_a"].ravel() >= 0
+        which = np.repeat(np.arange(n, dtype=np.int64), k)[keep]
+        value = r["best_value"].ravel()[keep]
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            terms = pd.DataFrame({"pair": which, "rank": np.tile(np.arange(1, k + 1, dtype=np.int64), n)[keep],
+                                  "via_a": src_index.take(r["best_a"].ravel()[keep]).to_numpy(),
+                                  "via_b": src_index.take(r["best_b"].ravel()[keep]).to_numpy(),
+                                  "similarity": value, "share": value / r["raw"][which]})
+            na, nb = np.diff(r["ptr_a"]), np.diff(r["ptr_b"])
+            # per pair a's neighbours, then b's: the two lists interleaved pair by pair
+            seg = np.concatenate([np.repeat(2 * np.arange(n), na), np.repeat(2 * np.arange(n) + 1, nb)])
+            order = np.argsort(seg, kind="stable")
+            pair_of = (seg // 2)[order].astype(np.int64)
+            sums = np.concatenate([r["sum_a"], r["sum_b"]])[order]
+            neighbors = pd.DataFrame({"pair": pair_of, "of": np.where(seg[order] % 2 == 0, "a", "b").astype(object),
+                                      "neighbor": src_index.take(np.concatenate([r["ids_a"], r["ids_b"]])[order]).to_numpy(),
+                                      "sum": sums, "share": sums / r["raw"][pair_of]})
+        return pairs, terms, neighbors
+
     @staticmethod
     def _rank_frame(first, who, index, ptr, tptr, tids, score, before, candidates, live=None):
         """Long frame (``first``, target, score, rank, candidates), one row per listed target; ``live``: per basket
