@@ -5,17 +5,17 @@ the device.
 two different nodes a, b iff ``S[a, b] >= t`` or ``S[b, a] >= t`` (iff (a, b) or (b, a) is a row of ``pairs(t)``).  One
 sweep of the iterate serves up to ``MAX_LEVELS`` thresholds; it reads the blocks a solver's ``_query.Reader`` describes in
 place and unites over them (one block on one GPU, one per virtual rank of a ``LocalWorld(P)``); N labels per threshold
-cross PCIe.  A pruned model (``_neighbors.NeighborSolver``) is answered on the host from its lists, for its matrix P.  No
+cross PCIe.  A pruned model (a solver with ``lists``) is answered on the host from its lists, for its matrix P.  No
 CPU fallback for the matrices: a missing library or device is an error.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
 import numbers
 
 import numpy as np
 
+from ._checks import finite
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
 from ._driver import Scratch, stage
 from ._profile import edges_f32
@@ -49,19 +49,10 @@ LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.ch
 def check_thresholds(t):
     """``components(t)``: one finite real number -> (float64 [1], True); a sequence of 1 to ``MAX_LEVELS`` of them ->
     (float64 array, False).  ValueError otherwise."""
-    def one(x):
-        try:
-            ok = not isinstance(x, (bool, np.bool_)) and isinstance(x, numbers.Real) and math.isfinite(float(x))
-        except OverflowError:                                # (an int too large for a float)
-            ok = False
-        if not ok:
-            raise ValueError(f"a threshold must be a finite number, not {x!r}")
-        return float(x)
-
     if isinstance(t, np.ndarray) and t.ndim == 0:
         t = t[()]                                            # a 0-d array holds one number
     if isinstance(t, numbers.Real) and not isinstance(t, (bool, np.bool_)):
-        return np.array([one(t)], dtype=np.float64), True
+        return np.array([finite(t, "a threshold")], dtype=np.float64), True
     if isinstance(t, (str, bytes, bool, np.bool_)):
         raise ValueError(f"a threshold must be a finite number or a sequence of them, not {t!r}")
     try:
@@ -70,7 +61,7 @@ def check_thresholds(t):
         raise ValueError(f"a threshold must be a finite number or a sequence of them, not {t!r}") from None
     if not 1 <= len(items) <= MAX_LEVELS:
         raise ValueError(f"components takes 1 to {MAX_LEVELS} thresholds, not {len(items)}")
-    return np.array([one(x) for x in items], dtype=np.float64), False
+    return np.array([finite(x, "a threshold") for x in items], dtype=np.float64), False
 
 
 # ---- the device path -----------------------------------------------------------------------------------------------------
@@ -159,11 +150,9 @@ def roots_of_lists(ids, vals, ts) -> np.ndarray:
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------
 def roots(solver, j, ts) -> np.ndarray:
     """[len(ts), n] of side j: per threshold every node's component as its smallest caller id."""
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        solver._reader(j)                                    # (raises when the tables were released)
-        ids, vals, _ = solver.tables[j].host()
-        return roots_of_lists(ids, vals, ts)
+    lists = solver.lists(j)
+    if lists is not None:
+        return roots_of_lists(lists[0], lists[1], ts)
     reader = solver._reader(j)
     if reader.n == 0:
         return np.empty((len(ts), 0), dtype=np.int64)

@@ -7,8 +7,8 @@ queues, per band, the three entries: ``simrank_explain_gather`` reads the iterat
 ``_query.Reader`` describes) into the band, ``simrank_explain_reduce`` adds up the rows, the columns and the whole of
 every piece, ``simrank_explain_select`` finds its k largest contributors.  Only the sums, the counts and the k best cross;
 the band stays on the device.  A side held in several column blocks (``LocalWorld(P)``) is packed into one temporary block
-once per call (``_model.detach``).  A pruned model (``_neighbors.NeighborSolver``) is answered on the host from its lists,
-for its matrix P.  No CPU fallback for the matrices: a missing library or device is an error.
+once per call (the solver's ``one_block`` scope).  A pruned model (a solver with ``lists``) is answered on the host from its
+lists, for its matrix P.  No CPU fallback for the matrices: a missing library or device is an error.
 
 The lists go to the device sorted by frame position, so that the position in a list, which is what the selection's order
 (value descending, i ascending, j ascending) compares, is the frame's order; ``explain`` hands the marginals back in the
@@ -17,10 +17,10 @@ order of the CSR row.
 from __future__ import annotations
 
 import ctypes as C
-import numbers
 
 import numpy as np
 
+from ._checks import is_int
 from ._companion import Companion
 from ._driver import Scratch, join, stage
 
@@ -51,13 +51,13 @@ LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.ch
 
 # ---- argument checks: nothing touches a device ---------------------------------------------------------------------------
 def check_k(k) -> int:
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, numbers.Integral) or not 1 <= int(k) <= MAX_K:
+    if not is_int(k) or not 1 <= int(k) <= MAX_K:
         raise ValueError(f"k must be an integer in 1 .. {MAX_K}, not {k!r}")
     return int(k)
 
 
 def check_max_terms(max_terms) -> int:
-    if isinstance(max_terms, (bool, np.bool_)) or not isinstance(max_terms, numbers.Integral) or int(max_terms) < 1:
+    if not is_int(max_terms) or int(max_terms) < 1:
         raise ValueError(f"max_terms must be a positive integer, not {max_terms!r}")
     return int(max_terms)
 
@@ -198,7 +198,6 @@ def run(reader, ptr_a, pos_a, ptr_b, pos_b, k, timing=None):
     (HIP events; serialises them)."""
     from . import _query
     (b,) = reader.blocks
-    assert b["cols"] == reader.n and b["rows"] == reader.n and b.get("col_lo", 0) == 0
     ops, lib, n = reader.ops, load(), int(ptr_a.size - 1)
     na, nb = np.diff(ptr_a), np.diff(ptr_b)
     terms = na * nb
@@ -239,19 +238,6 @@ def run(reader, ptr_a, pos_a, ptr_b, pos_b, k, timing=None):
     return row_sum, col_sum, raw, count, bi, bj, bv
 
 
-def _with_one_block(solver, j, go):
-    """``go(reader)`` on side j's reader, packed into one temporary block first when it is held in several."""
-    from . import _model
-    reader = solver._reader(j)
-    if len(reader.blocks) == 1:
-        return go(reader)
-    temp = _model.detach(solver)                             # several column blocks: one temporary block, once per call
-    try:
-        return go(temp._reader(j))
-    finally:
-        temp.release()
-
-
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------
 def explain(solver, j, src_j, spec, ia, ib, k, max_terms, labels=None, timing=None):
     """What ``_KeptModel.explain`` builds its frames from, for the pairs (``ia``, ``ib``: caller ids of side j) whose
@@ -259,7 +245,6 @@ def explain(solver, j, src_j, spec, ia, ib, k, max_terms, labels=None, timing=No
     contributors, common, evidence, raw, propagated), the lists (ptr_a, ids_a, ptr_b, ids_b: caller ids of side src_j in
     the CSR rows' order) with their marginals (sum_a, sum_b), and the k best (best_a, best_b: caller ids of side src_j or
     -1, best_value).  ``labels``: names the pair a refusal speaks of."""
-    from ._neighbors import NeighborSolver
     ia, ib = np.asarray(ia, dtype=np.int64), np.asarray(ib, dtype=np.int64)
     n = int(ia.size)
     ptr_a, ids_a = lists_of(spec.csr, ia)
@@ -273,14 +258,13 @@ def explain(solver, j, src_j, spec, ia, ib, k, max_terms, labels=None, timing=No
                          f"{int(terms[p])} terms, more than max_terms = {max_terms}")
     sorted_a, back_a = sorted_lists(ptr_a, ids_a)
     sorted_b, back_b = sorted_lists(ptr_b, ids_b)
-    if isinstance(solver, NeighborSolver):
-        solver._reader(src_j)                                # (raises when the tables were released)
-        tables = solver.tables[src_j].host()
+    tables = solver.lists(src_j)
+    if tables is not None:
         out = run_lists(tables, ptr_a, sorted_a, ptr_b, sorted_b, k)
-        own = tables if src_j == j else solver.tables[j].host()
-        similarity = pairs_of_lists(own, ia, ib)
+        similarity = pairs_of_lists(tables if src_j == j else solver.lists(j), ia, ib)
     else:
-        out = _with_one_block(solver, src_j, lambda reader: run(reader, ptr_a, sorted_a, ptr_b, sorted_b, k, timing))
+        with solver.one_block(src_j) as reader:
+            out = run(reader, ptr_a, sorted_a, ptr_b, sorted_b, k, timing)
         similarity = solver.pair_values(j, ia.astype(np.int32), ib.astype(np.int32))
     row_sum, col_sum, raw, count, bi, bj, bv = out
     scale = np.asarray(spec.rowscale, dtype=np.float64)

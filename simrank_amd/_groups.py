@@ -5,9 +5,9 @@ for any labelling of the fitted nodes: per node the mean similarity to the other
 mean similarity to another cluster and that cluster.  One sweep of the iterate in place (the block a solver's
 ``_query.Reader`` describes, in solver order with its column map); three numbers per node cross PCIe, or with
 ``cluster_means`` the N x K means.  A side held in several column blocks (``LocalWorld(P)``) is first packed into one
-temporary block (``_model.detach``), as ``_neighbors.prune`` does.  A pruned model (``_neighbors.NeighborSolver``) is
-answered on the host from its lists, for its matrix P.  No CPU fallback for the matrices: a missing library or device is
-an error.
+temporary block (the solver's ``one_block`` scope), as ``_neighbors.prune`` does.  A pruned model (a solver with
+``lists``) is answered on the host from its lists, for its matrix P.  No CPU fallback for the matrices: a missing library
+or device is an error.
 
 The definitions (include/simrank_groups.h states them for a block; here for a model).  For node a and cluster g,
 ``M_g(a) = {b : labels[b] = g, b != a}``; ``sum(a, g)`` is the float64 sum of ``S[a, b]`` over it (row a: the element
@@ -20,10 +20,10 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
 
 import numpy as np
 
+from ._checks import is_int
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
 from ._driver import Scratch, stage
 
@@ -58,7 +58,7 @@ def _integers(values) -> np.ndarray:
         raise ValueError(f"labels must be one-dimensional, not of shape {a.shape}")
     if a.dtype == object:
         for x in a:
-            if isinstance(x, (bool, np.bool_)) or not isinstance(x, numbers.Integral):
+            if not is_int(x):
                 raise ValueError(f"a cluster label must be an integer, not {x!r}")
         try:
             return np.array([int(x) for x in a], dtype=np.int64)
@@ -105,7 +105,7 @@ def check_labels(labels, index) -> np.ndarray:
 
 
 def check_max_bytes(max_bytes) -> int:
-    if isinstance(max_bytes, (bool, np.bool_)) or not isinstance(max_bytes, numbers.Integral) or max_bytes < 1:
+    if not is_int(max_bytes) or max_bytes < 1:
         raise ValueError(f"max_bytes must be a positive integer, not {max_bytes!r}")
     return int(max_bytes)
 
@@ -167,8 +167,7 @@ def compose(reader, gidx, sizes):
 def scores_reader(reader, gidx, sizes, want_means=False, timing=None):
     """(own, other, nearest rank or -1, means or None) in the caller's order, of a reader whose one block holds every
     column."""
-    b = reader.blocks[0]
-    assert len(reader.blocks) == 1 and b["cols"] == reader.n and b["rows"] == reader.n and b.get("col_lo", 0) == 0
+    (b,) = reader.blocks
     own_p, other_p, near_p, means_p = means_block(reader.ops, b, *compose(reader, gidx, sizes), want_means, timing)
     n = reader.n
     own, other, nearest = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int64)
@@ -229,20 +228,11 @@ def scores_of_lists(ids, vals, gidx, sizes, want_means=False):
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------
 def scores(solver, j, gidx, sizes, want_means=False):
     """(own, other, nearest rank or -1, means or None) of side j, in the caller's order."""
-    from . import _model
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        solver._reader(j)                                    # (raises when the tables were released)
-        ids, vals, _ = solver.tables[j].host()
-        return scores_of_lists(ids, vals, gidx, sizes, want_means)
-    reader = solver._reader(j)
-    if len(reader.blocks) == 1:
+    lists = solver.lists(j)
+    if lists is not None:
+        return scores_of_lists(lists[0], lists[1], gidx, sizes, want_means)
+    with solver.one_block(j) as reader:
         return scores_reader(reader, gidx, sizes, want_means)
-    temp = _model.detach(solver)                             # several column blocks: one temporary block, as prune packs it
-    try:
-        return scores_reader(temp._reader(j), gidx, sizes, want_means)
-    finally:
-        temp.release()
 
 
 # ---- host arithmetic on the three numbers ------------------------------------------------------------------------------------

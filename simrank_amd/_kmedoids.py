@@ -8,8 +8,8 @@ is K medoid rows against all N columns (``simrank_kmedoids_assign``), the update
 ``simrank_kmedoids_pick``.  Per iteration N int32 labels come to the host, which regroups them as ``_groups.compose`` does
 and sends the lists back, and two 4-byte counters come down; ``own``, the medoid rows and the per-node values stay on the
 device.  A side held in several column blocks (``LocalWorld(P)``) is packed into one temporary block once per call
-(``_model.detach``).  A pruned model (``_neighbors.NeighborSolver``) is answered on the host from its lists, for its
-matrix P.  No CPU fallback for the matrices: a missing library or device is an error.
+(the solver's ``one_block`` scope).  A pruned model (a solver with ``lists``) is answered on the host from its lists, for
+its matrix P.  No CPU fallback for the matrices: a missing library or device is an error.
 
 The definitions (include/simrank_kmedoids.h states them for a block; here for a model).  ``v(j, a) = S[m_j, a]``: row
 m_j, the element ``similarity(m_j, a)`` reads, compared in float64; candidates in the order (v descending, j ascending),
@@ -20,12 +20,12 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import numbers
 import time
 
 import numpy as np
 
 from . import _groups
+from ._checks import is_int
 from ._companion import Companion
 from ._driver import Scratch, stage
 
@@ -81,7 +81,7 @@ def check_seeds(seeds, index) -> np.ndarray:
 
 
 def check_max_iter(max_iter) -> int:
-    if isinstance(max_iter, (bool, np.bool_)) or not isinstance(max_iter, numbers.Integral) or max_iter < 1:
+    if not is_int(max_iter) or max_iter < 1:
         raise ValueError(f"max_iter must be a positive integer, not {max_iter!r}")
     return int(max_iter)
 
@@ -97,12 +97,6 @@ def _clock(timing, name, t0):
         timing[name] = timing.get(name, 0.0) + (time.perf_counter() - t0) * 1e3
 
 
-def _one_block(reader):
-    b = reader.blocks[0]
-    assert len(reader.blocks) == 1 and b["cols"] == reader.n and b["rows"] == reader.n and b.get("col_lo", 0) == 0
-    return b
-
-
 def _assign(lib, ops, b, med, k, current, cluster, value, moved, timing):
     """Queue one assignment.  ``med`` serves as med_row and med_col: in a one-block reader a node's row is its column."""
     stage(ops, timing, "assign_ms", lambda: check(lib.simrank_kmedoids_assign(
@@ -112,7 +106,7 @@ def _assign(lib, ops, b, med, k, current, cluster, value, moved, timing):
 
 def assign_reader(reader, seeds, timing=None):
     """(cluster int64 [N], value float64 [N]) in the caller's order: the first assignment to the seeds (caller ids)."""
-    b, ops, n, k = _one_block(reader), reader.ops, reader.n, int(seeds.size)
+    (b,), ops, n, k = reader.blocks, reader.ops, reader.n, int(seeds.size)
     lab, val = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.float64)
     with Scratch(ops) as scratch:
         med = scratch.put(reader.inv[seeds].astype(np.int32))
@@ -130,7 +124,7 @@ def loop_reader(reader, seeds, max_iter, timing=None):
     objective)]).  ``value`` is what the last assignment read; None when the medoids moved after it (``max_iter`` ran
     out).  ``timing``: a dict that receives the milliseconds of the stages, added up over the iterations (HIP events for
     the kernels, which serialises them; the host clock for the regroup and its copies)."""
-    b, ops, n, k = _one_block(reader), reader.ops, reader.n, int(seeds.size)
+    (b,), ops, n, k = reader.blocks, reader.ops, reader.n, int(seeds.size)
     lib, groups = load(), _groups.load()
     hist_rows = min(max_iter, HISTORY_ROWS)
     zero, got = np.zeros(2, dtype=np.uint32), np.empty(2, dtype=np.uint32)
@@ -277,45 +271,27 @@ def loop_lists(ids, vals, diag, seeds, max_iter):
 
 
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------
-def _with_one_block(solver, j, run):
-    """``run(reader)`` on side j's reader, packed into one temporary block first when it is held in several."""
-    from . import _model
-    reader = solver._reader(j)
-    if len(reader.blocks) == 1:
-        return run(reader)
-    temp = _model.detach(solver)                             # several column blocks: one temporary block, once per call
-    try:
-        return run(temp._reader(j))
-    finally:
-        temp.release()
-
-
 def assign(solver, j, seeds):
     """(cluster int64 [N], value float64 [N]) of side j, in the caller's order."""
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        solver._reader(j)                                    # (raises when the tables were released)
-        ids, vals, diag = solver.tables[j].host()
-        return assign_rows(rows_of_lists(ids, vals, diag, seeds), seeds)[:2]
-    return _with_one_block(solver, j, lambda reader: assign_reader(reader, seeds))
+    lists = solver.lists(j)
+    if lists is not None:
+        return assign_rows(rows_of_lists(*lists, seeds), seeds)[:2]
+    with solver.one_block(j) as reader:
+        return assign_reader(reader, seeds)
 
 
 def kmedoids(solver, j, seeds, max_iter):
     """(cluster, medoids, value, sizes, cohesion, history) of side j as ``loop_reader`` returns them, ``value`` read again
     for the final medoids where the loop left it open."""
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        solver._reader(j)
-        ids, vals, diag = solver.tables[j].host()
-        out = loop_lists(ids, vals, diag, seeds, max_iter)
+    lists = solver.lists(j)
+    if lists is not None:
+        out = loop_lists(*lists, seeds, max_iter)
         if out[2] is None:
-            V = rows_of_lists(ids, vals, diag, out[1])
+            V = rows_of_lists(*lists, out[1])
             out = out[:2] + (V[out[0], np.arange(V.shape[1])],) + out[3:]
         return out
-
-    def run(reader):
+    with solver.one_block(j) as reader:
         out = loop_reader(reader, seeds, max_iter)
         if out[2] is None:                                   # max_iter ran out: every node's element of its final medoid's row
             out = out[:2] + (reader.pair_values(out[1][out[0]], np.arange(reader.n)),) + out[3:]
         return out
-    return _with_one_block(solver, j, run)

@@ -5,17 +5,16 @@ found on the device.
 the height ``w(a, b) = max(S[a, b], S[b, a])`` (NaN is no entry, -0.0 and +0.0 are one height); the dendrogram is a maximum
 spanning forest of that graph and every ``components(t)`` a cut of it.  The device finds A forest in at most ceil(log2 n)
 Boruvka rounds, each one sweep of the blocks a solver's ``_query.Reader`` describes, in place; ``canonical`` turns any
-valid forest into the one table the matrix defines.  A pruned model (``_neighbors.NeighborSolver``) is answered on the
+valid forest into the one table the matrix defines.  A pruned model (a solver with ``lists``) is answered on the
 host from its lists.  No CPU fallback for the matrices: a missing library or device is an error.
 """
 from __future__ import annotations
 
 import ctypes as C
-import math
-import numbers
 
 import numpy as np
 
+from ._checks import finite, is_int
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
 from ._driver import Scratch, stage
 from ._profile import edges_f32
@@ -50,21 +49,9 @@ LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.ch
 
 
 # ---- argument checks: nothing touches a device ---------------------------------------------------------------------------
-def _finite(x, what):
-    if isinstance(x, np.ndarray) and x.ndim == 0:
-        x = x[()]                                            # a 0-d array holds one number
-    try:
-        ok = not isinstance(x, (bool, np.bool_)) and isinstance(x, numbers.Real) and math.isfinite(float(x))
-    except OverflowError:                                    # (an int too large for a float)
-        ok = False
-    if not ok:
-        raise ValueError(f"{what} must be a finite number, not {x!r}")
-    return float(x)
-
-
 def check_floor(min_similarity):
     """``linkage(min_similarity)``: None, or one finite real number as a float.  ValueError otherwise."""
-    return None if min_similarity is None else _finite(min_similarity, "min_similarity")
+    return None if min_similarity is None else finite(min_similarity, "min_similarity")
 
 
 def check_cut(t, n_clusters):
@@ -72,9 +59,9 @@ def check_cut(t, n_clusters):
     if (t is None) == (n_clusters is None):
         raise ValueError("cut takes exactly one of t and n_clusters")
     if t is not None:
-        return _finite(t, "t"), None
+        return finite(t, "t"), None
     k = n_clusters
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, numbers.Integral) or k < 1:
+    if not is_int(k) or k < 1:
         raise ValueError(f"n_clusters must be an int >= 1, not {k!r}")
     return None, int(k)
 
@@ -246,18 +233,16 @@ def forest_of_lists(ids, vals, floor: float):
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------
 def check_solver(solver, floor):
     """What ``linkage`` refuses of a model before any work: a pruned model without a positive floor."""
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver) and not (floor is not None and floor > 0):
+    if getattr(solver, "kept_k", None) is not None and not (floor is not None and floor > 0):
         raise ValueError("linkage of a pruned model needs min_similarity > 0: the entries a pruned model does not keep are "
                          "+0.0 and tie everything at 0")
 
 
 def table(solver, j, floor):
     """(n, left, right, similarity, size) of side j: the canonical rows over the caller's ids."""
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        solver._reader(j)                                    # (raises when the tables were released)
-        ids, vals, _ = solver.tables[j].host()
+    lists = solver.lists(j)
+    if lists is not None:
+        ids, vals, _ = lists
         return (len(ids),) + canonical(len(ids), *forest_of_lists(ids, vals, floor))
     reader = solver._reader(j)
     if reader.n == 0:

@@ -4,7 +4,8 @@ holds one packed matrix per side (``DetachedSolver``), and the file a model is s
 ``detach`` packs every side of a kept solver's iterate into one device block in the caller's order (f32 row-major,
 fp16-held 64-column panels or float64 row-major) through ``simrank_model_pack``; ``DetachedSolver`` answers every query
 of ``_query.SolverQueries`` on that block with identity orders (no column maps), and ``fold_in`` from the few host arrays
-of the specs.  ``save`` / ``load`` write and read such a solver as one file: a JSON header and raw little-endian arrays,
+of the specs.  ``detach`` is also what ``_query.SolverQueries.one_block`` packs a side held in several column blocks
+with, for the one call that needs one block; ``_kept`` calls it for ``compact`` and ``save``.  ``save`` / ``load`` write and read such a solver as one file: a JSON header and raw little-endian arrays,
 moved between the device and the file in bands.  No CPU fallback: a missing library or device is an error.
 """
 from __future__ import annotations

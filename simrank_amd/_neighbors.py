@@ -4,8 +4,10 @@ OTHER nodes of every node, and the solver that answers the queries of a kept mod
 The pruned form of a side of n nodes is two tables [n][k] (int32 ids in the caller's order, float64 values; id -1 / value 0
 past the candidates) and the diagonal [n].  They stand for the matrix P that holds the kept entries, the diagonal and +0.0
 everywhere else; every query of ``NeighborSolver`` is the same query of a dense model on P, bit for bit.  ``select`` builds
-the tables from the block(s) of a kept iterate with ``simrank_neighbors_select``, whose cost does not grow with k.  No CPU
-fallback: a missing library or device is an error.
+the tables from the block(s) of a kept iterate with ``simrank_neighbors_select``, whose cost does not grow with k.  The
+queries with a host path of their own (``components``, ``linkage``, ``count_pairs``, ``cluster_quality``, ``kmedoids``,
+``explain``) ask any solver for ``lists(j)``: ``NeighborSolver`` alone answers with its tables, so nothing outside this
+module tests for the class.  No CPU fallback: a missing library or device is an error.
 """
 from __future__ import annotations
 
@@ -267,12 +269,16 @@ class NeighborSolver(SolverQueries):
             raise ValueError("a pruned model holds the k most similar OTHER nodes")
         return self.topk_of(j, np.arange(self.n[j], dtype=np.int32), k)
 
+    def lists(self, j):
+        """Side j's tables on the host, (ids, values, diag): what answers a query of a pruned model."""
+        self._reader(j)                                      # (raises when the tables were released)
+        return self.tables[j].host()
+
     def pairs(self, j, t, max_pairs):
         """Side j's kept off-diagonal entries at least ``t``: (offsets [n + 1], neighbour ids ascending within a node,
         values), on the host after one copy of the tables."""
         from ._select import too_many
-        self._reader(j)
-        ids, vals, _ = self.tables[j].host()
+        ids, vals, _ = self.lists(j)
         hit = (ids >= 0) & (vals >= float(t))
         counts = hit.sum(axis=1)
         total = int(counts.sum())
@@ -318,25 +324,19 @@ class NeighborSolver(SolverQueries):
 
 def prune(solver, k) -> NeighborSolver:
     """A ``NeighborSolver`` holding the k best neighbours of every node of every side of ``solver`` (a kept plan solver
-    or a ``_model.DetachedSolver``); ``solver`` is left as it is.  A side held in several column blocks is first packed
-    into a temporary block (``_model.detach``): the selection reads one block that holds every column."""
+    or a ``_model.DetachedSolver``); ``solver`` is left as it is.  Sides held in several column blocks are first packed
+    into one temporary block each, once for the model (``one_block``): the selection reads one block that holds every
+    column."""
     from . import _model
-    sides = range(len(solver.n))
-    temp = None
     tables = []
     try:
-        if any(len(solver._reader(j).blocks) != 1 for j in sides):
-            temp = _model.detach(solver)
-        src = temp or solver
-        for j in sides:
-            tables.append(select(src._reader(j), k))
+        with solver.one_block() as readers:
+            for reader in readers:
+                tables.append(select(reader, k))
     except Exception:
         for t in tables:
             t.free()
         raise
-    finally:
-        if temp is not None:
-            temp.release()
     if isinstance(solver, _model.DetachedSolver):
         specs, fitted = solver.specs, solver.fitted
     else:

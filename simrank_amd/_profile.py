@@ -5,7 +5,7 @@ counted on the device.
 ``threshold_for`` answers "which threshold gives me at most M pairs?" with a global radix select whose number of sweeps
 depends only on the stored type (3 for f32, 2 for fp16-held, 6 for float64).  Both read the blocks a solver's
 ``_query.Reader`` describes in place and add over them (one block on one GPU, one per virtual rank of a
-``LocalWorld(P)``).  A pruned model (``_neighbors.NeighborSolver``) is answered on the host from its lists: N x k values
+``LocalWorld(P)``).  A pruned model (a solver with ``lists``) is answered on the host from its lists: N x k values
 plus the absent +0.0 entries, added by arithmetic.  No CPU fallback for the matrices: a missing library or device is an
 error.
 """
@@ -17,6 +17,7 @@ import numbers
 
 import numpy as np
 
+from ._checks import is_finite_real, is_int
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
 from ._driver import Scratch, stage
 
@@ -70,14 +71,14 @@ def check_thresholds(thresholds) -> np.ndarray:
     if not 1 <= len(items) <= MAX_EDGES:
         raise ValueError(f"count_pairs takes 1 to {MAX_EDGES} thresholds, not {len(items)}")
     for t in items:
-        if isinstance(t, (bool, np.bool_)) or not isinstance(t, numbers.Real) or not math.isfinite(float(t)):
+        if not is_finite_real(t):
             raise ValueError(f"every threshold must be a finite number, not {t!r}")
     return np.array([float(t) for t in items], dtype=np.float64)
 
 
 def check_max_pairs(max_pairs) -> int:
     """``threshold_for(max_pairs)``: an integer >= 1 (ValueError otherwise)."""
-    if isinstance(max_pairs, (bool, np.bool_)) or not isinstance(max_pairs, numbers.Integral) or int(max_pairs) < 1:
+    if not is_int(max_pairs) or int(max_pairs) < 1:
         raise ValueError(f"max_pairs must be a positive integer, not {max_pairs!r}")
     return int(max_pairs)
 
@@ -217,19 +218,17 @@ def threshold_blocks(ops, blocks, max_pairs: int, timing=None):
 
 
 # ---- a solver's side ---------------------------------------------------------------------------------------------------------
-def _lists(solver, j):
-    """A pruned side on the host: (the kept off-diagonal values, the number of absent +0.0 entries)."""
-    solver._reader(j)                                        # (raises when the tables were released)
-    ids, vals, _ = solver.tables[j].host()
+def _kept_values(ids, vals):
+    """A pruned side's lists -> (the kept off-diagonal values, the number of absent +0.0 entries)."""
     kept = ids >= 0
-    n = solver.n[j]
+    n = len(ids)
     return vals[kept], n * (n - 1) - int(kept.sum())
 
 
 def count_pairs(solver, j, ts) -> np.ndarray:
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        vals, zeros = _lists(solver, j)
+    lists = solver.lists(j)
+    if lists is not None:
+        vals, zeros = _kept_values(lists[0], lists[1])
         return np.array([int((vals >= t).sum()) + (zeros if 0.0 >= t else 0) for t in ts], dtype=np.int64)
     reader = solver._reader(j)
     if reader.n == 0:
@@ -238,10 +237,9 @@ def count_pairs(solver, j, ts) -> np.ndarray:
 
 
 def threshold_for(solver, j, max_pairs: int):
-    from ._neighbors import NeighborSolver
-    if isinstance(solver, NeighborSolver):
-        vals, zeros = _lists(solver, j)
-        return select_values(vals, zeros, max_pairs)
+    lists = solver.lists(j)
+    if lists is not None:
+        return select_values(*_kept_values(lists[0], lists[1]), max_pairs)
     reader = solver._reader(j)
     if reader.n == 0:
         return math.inf, 0

@@ -7,9 +7,10 @@ fallback: a missing library or device is an error.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import numbers
 
+from ._checks import is_int
 from ._companion import PANEL_F16, PANEL_F32, ROWMAJOR_F32, ROWMAJOR_F64, Companion  # noqa: F401 (a block's layouts)
 from ._driver import Scratch, bands, scatter_blocks, stage
 
@@ -41,7 +42,7 @@ LIB_PATH, HEADER_PATH, load, check = _c.lib_path, _c.header_path, _c.load, _c.ch
 
 def check_k(k):
     """``most_similar(nodes, k)`` / ``top_k(k)``: k a positive integer (ValueError otherwise; nothing touches a device)."""
-    if isinstance(k, bool) or not isinstance(k, numbers.Integral) or int(k) < 1:
+    if not is_int(k) or int(k) < 1:
         raise ValueError(f"k must be a positive integer, not {k!r}")
     return int(k)
 
@@ -76,8 +77,10 @@ def clamp_k(n, k, exclude_diag=True) -> int:
 
 
 class SolverQueries:
-    """What a kept solver (``cplan.PlanSolver``, ``cshard.CShardSolver``, ``cdouble.F64Solver``) answers node queries
-    with: one ``Reader`` per side, made on first use by the solver's ``_make_reader(j)`` and closed at ``release``."""
+    """What a kept solver (``cplan.PlanSolver``, ``cshard.CShardSolver``, ``cdouble.F64Solver``, ``_model.DetachedSolver``,
+    ``_neighbors.NeighborSolver``) answers node queries with: one ``Reader`` per side, made on first use by the solver's
+    ``_make_reader(j)`` and closed at ``release``; and the two decisions every query of a side makes first: ``lists``
+    (is this a pruned model, answered on the host?) and ``one_block`` (is the side held in several column blocks?)."""
 
     _readers = None
     _folders = None
@@ -88,6 +91,32 @@ class SolverQueries:
         if j not in self._readers:
             self._readers[j] = self._make_reader(j)
         return self._readers[j]
+
+    def lists(self, j):
+        """None: side j is held as a matrix.  The solver of a pruned model returns its host lists (ids, values, diag)
+        here, and the query is answered from them on the host."""
+        return None
+
+    @contextlib.contextmanager
+    def one_block(self, j=None):
+        """Side j's reader where its one block holds every row and column; a side held in several column blocks
+        (``LocalWorld(P)``) is first packed into a temporary ``_model.detach(self)``, every side in the model's own
+        storage, which is released at the end of the scope, with or without an exception.  Without ``j``: the readers
+        of all sides, packed at most once."""
+        from . import _model
+        sides = range(len(self.n)) if j is None else [j]
+        temp = None
+        try:
+            if any(len(self._reader(i).blocks) != 1 for i in sides):
+                temp = _model.detach(self)
+            readers = [(temp or self)._reader(i) for i in sides]
+            for r in readers:
+                (b,) = r.blocks
+                assert b["cols"] == r.n and b["rows"] == r.n and b.get("col_lo", 0) == 0
+            yield readers if j is None else readers[0]
+        finally:
+            if temp is not None:
+                temp.release()
 
     def rows(self, j, node_ids):
         """float64 [len(node_ids), n]: side j's rows of those nodes (caller's ids), columns in the caller's order."""
