@@ -1116,6 +1116,8 @@ int simrank_graph_get(const simrank_graph* g, const char* key, int64_t* value) {
     SR_REQUIRE(g && key && value, "NULL argument");
     if (!strcmp(key, "fused_ids16")) *value = g->fused ? g->fused->ids16 : -1;
     else if (!strcmp(key, "gather_ids16")) *value = (g->col16 && g->tun.ids16) ? 1 : 0;
+    else if (!strcmp(key, "leg2_short_groups")) *value = g->short_groups;
+    else if (!strcmp(key, "leg2_short_taken")) *value = g->leg2_short_taken;
     else SR_REQUIRE(false, "unknown graph key '%s'", key);
     return SIMRANK_OK;
 }

@@ -14,7 +14,8 @@ No tolerance is involved anywhere: the float64 NumPy result cast to float32 is T
 `summable_symmetric` builds a symmetric S whose leg-1 AND leg-2 operands satisfy it (so W.(W.S)^T is exactly symmetric and
 exactly summable: what the upper-triangle forms need), `exact_epilogue` is the oracle's epilogue expression with a check
 that no intermediate of any association rounds in float32, `plant_previous` puts differences of exactly eps, eps + one step
-and eps - one step at chosen places, `regular_graph` / `exact_updates` give whole fits whose iterates stay exact.
+and eps - one step at chosen places, `regular_graph` / `exact_updates` give whole fits whose iterates stay exact;
+`short_lengths` / `short_case` / `tie_places_every_row` are the graphs, operands and tie places built for leg 2's short path.
 """
 from collections import namedtuple
 
@@ -479,6 +480,12 @@ def leg2_case(n, variant, mantissa=24, seed=None, exponent=0):
     """-> (csr, Symmetric, counts or None, prior or None, lbd, want float64) of a symmetric leg 2 with the epilogue."""
     seed = n if seed is None else seed
     csr = corner_case(n, n, seed, hubs=min(n, 150))
+    return leg2_on(csr, variant, mantissa, seed, exponent)
+
+
+def leg2_on(csr, variant, mantissa=24, seed=0, exponent=0):
+    """leg2_case on a given square pattern (row scales powers of two)."""
+    n = csr.n_rows
     h = HEADROOM[variant] if mantissa == 24 else 0
     sym = summable_symmetric(csr, mantissa=mantissa, headroom=h, seed=seed, exponent=exponent)
     counts = epilogue_counts((n, n), seed, symmetric=True) if variant != "plain" else None
@@ -491,6 +498,89 @@ def leg2_case(n, variant, mantissa=24, seed=None, exponent=0):
     want = exact_epilogue(product64(csr, sym.Tt), 0.5, counts, prior, lbd)
     assert np.array_equal(want, want.T)
     return csr, sym, counts, prior, lbd, want
+
+
+# ---- graphs built for leg 2's short path (tests/test_gpu_exact_short.py; the rule: tests/leg2_rule.py) -------------------
+SHORT_WIDTHS = (0, 8, 16)
+SHORT_EPS = 1.0                                          # as EPS of tests/test_gpu_exact_kernels.py
+# The longest row of the heavy-row graph.  400 (tests/leg2_short_worker.py) holds summable_symmetric's integer assertion
+# with the 19 bits that the "all" variant leaves; were it to fail there, this is the number to lower.
+HEAVY_ROW = 400
+
+
+def short_lengths():
+    """name -> (row lengths in the caller's order, seed of the columns): the smallest shapes at which each new thing of
+    short_group3 / build_short_image can go wrong.
+    boundary   660 rows: groups short at both widths, at 16 only, never; rows of exactly 0, 8, 9, 16, 17 entries, a wholly
+               empty tile, a ragged last tile of 20 rows (a multiple of 4: the vector mirror store with r4 < nrows) and a
+               last panel of 20 columns (the scalar mirror store)
+    ragged21   the same with 21 rows in the last tile (the scalar mirror store in whole panels too); ragged1: with 1 row
+    n64        the smallest graph with an image: ONE group of two tiles, tiles 2 and 3 of the image are padding
+    n63        no image (and no upper-triangle form): everything the rule counts is 0
+    n129       a general group (one row of 17 entries) and a second group that is one tile of one row, short
+    heavy_row  700 rows, one of HEAVY_ROW entries whose block is cut: cut tiles beside short groups, groups off the 128-row grid
+    equal8 / equal16   150 rows of exactly 8 / 16 entries: within a tile the image's order is the reverse row order."""
+    from tests import leg2_rule as R
+    rng = np.random.default_rng(31)
+    one = R.boundary_lengths(1)
+    one[-1] = 5                                          # (a last row with entries: the 1-row tile does something)
+    n64 = rng.integers(0, 9, 64)
+    n64[[3, 40]] = 8
+    n63 = rng.integers(0, 9, 63)
+    n129 = rng.integers(0, 9, 129)
+    n129[70], n129[128] = 17, 7
+    return {"boundary": (R.boundary_lengths(20), 22), "ragged21": (R.boundary_lengths(21), 22), "ragged1": (one, 22),
+            "n64": (n64.tolist(), 64), "n63": (n63.tolist(), 63), "n129": (n129.tolist(), 129),
+            "heavy_row": (R.heavy_row_lengths(HEAVY_ROW), 24), "equal8": ([8] * 150, 41), "equal16": ([16] * 150, 42)}
+
+
+SHORT_GRAPHS = ("boundary", "ragged21", "ragged1", "n64", "n63", "n129", "heavy_row", "equal8", "equal16")
+SHORT_EQUAL = ("equal8", "equal16")
+_short = {}
+
+
+def short_case(name, variant):
+    """leg2_case on short_lengths()[name]: -> (csr, Symmetric, counts, prior, lbd, want float64, row lengths).  Built once
+    per (name, variant) and shared: nobody writes to what this returns."""
+    key = (name, variant)
+    if key not in _short:
+        from tests import leg2_rule as R
+        lengths, seed = short_lengths()[name]
+        csr = pow2_rowscale(R.from_lengths(lengths, seed), seed)
+        assert np.array_equal(np.diff(csr.rowptr), lengths)
+        _short[key] = leg2_on(csr, variant, seed=seed) + (list(lengths),)
+    return _short[key]
+
+
+def tie_places_every_row(n, panel=32):
+    """For EVERY row a: the diagonal, the first and the last column of a's own 32-column block, column n - 1 and one column
+    of another panel, (7 a + 3) % n — about 5 n places, so every slot of every pass of every lane group of every tile
+    holds a tie, on both sides of the diagonal (the upper-triangle forms compute (a, c) at row min(a, c))."""
+    out, seen = [], set()
+    for a in range(n):
+        b0 = a // panel * panel
+        for c in (a, b0, min(n - 1, b0 + panel - 1), n - 1, (7 * a + 3) % n):
+            if (a, c) not in seen:
+                seen.add((a, c))
+                out.append((a, c))
+    return out
+
+
+_planted = {}
+
+
+def short_planted(name, variant):
+    """-> (want float32, Planted with all three kinds, Planted with "on" and "below" only) at tie_places_every_row; once."""
+    key = (name, variant)
+    if key not in _planted:
+        want = short_case(name, variant)[5]
+        want32 = want.astype(np.float32)
+        assert np.array_equal(want32.astype(np.float64), want)
+        places = tie_places_every_row(want.shape[0])
+        p = plant_previous(want32, SHORT_EPS, places, symmetric=True)
+        q = plant_previous(want32, SHORT_EPS, places, symmetric=True, only=("on", "below"))
+        _planted[key] = (want32, p, q)
+    return _planted[key]
 
 
 # ---- the count on fp16-held matrices (half.hip's header) ------------------------------------------------------------

@@ -16,7 +16,7 @@ sys.path.insert(0, sys.argv[1])
 from oracle import simrank_oracle as O  # noqa: E402
 from simrank_amd import ingest, synth  # noqa: E402
 from simrank_amd.engine import HipOps, Plan  # noqa: E402
-from simrank_amd.ingest import CSR  # noqa: E402
+from tests.leg2_rule import boundary_lengths, from_lengths, heavy_row_lengths, short_groups, tiles_of  # noqa: E402
 
 UPDATES = 5
 CONVERGE_UPDATES = 18
@@ -30,89 +30,14 @@ def from_frame(df):
     return ingest.directed(df, False, "from", "to", "weight")[1]
 
 
-def from_lengths(lengths, seed):
-    """Rows of exactly these lengths, columns drawn without repetition; the plan keeps the order (reorder = False)."""
-    n = len(lengths)
-    rng = np.random.default_rng(seed)
-    rows = [np.sort(rng.choice(n, size=k, replace=False)).astype(np.int32) for k in lengths]
-    rowptr = np.zeros(n + 1, dtype=np.int32)
-    rowptr[1:] = np.cumsum(lengths)
-    col = np.concatenate(rows + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
-    deg = np.asarray(lengths, dtype=np.float64)
-    return CSR(n, n, rowptr, col, np.where(deg > 0, 1.0 / np.maximum(deg, 1), 0.0))
-
-
 def boundary_graph():
-    """Groups of four 32-row tiles (one workgroup each) at the edges of both widths, then a ragged last tile:
-    0: rows of 0..8 entries, one tile wholly empty            short at 8 and at 16
-    1: three tiles of <= 8, one tile with rows of exactly 9   general path at 8, short at 16
-    2: rows of exactly 16 and fewer                           short at 16 only
-    3: three tiles of <= 8, one tile with a row of 17         never short
-    4: rows of exactly 8                                      short at both
-    5: 20 rows of <= 8 (the ragged last tile)                 short at both"""
-    rng = np.random.default_rng(21)
-    g0 = np.concatenate([rng.integers(0, 9, 32), np.full(32, 8), np.zeros(32, int), rng.integers(0, 9, 32)])
-    # (no 32-row block above 256 entries: build_tiles would cut it, and a cut tile is never short)
-    g1 = np.concatenate([rng.integers(0, 9, 64), np.full(16, 9), rng.integers(1, 9, 48)])
-    g2 = np.concatenate([np.full(8, 16), rng.integers(0, 9, 24), rng.integers(0, 9, 96)])
-    g2[40] = 16
-    t17 = rng.integers(0, 9, 32)
-    t17[5] = 17
-    g3 = np.concatenate([rng.integers(0, 9, 32), t17, rng.integers(0, 9, 64)])
-    g4 = np.full(128, 8)
-    g5 = rng.integers(0, 9, 20)
-    return from_lengths(np.concatenate([g0, g1, g2, g3, g4, g5]).astype(int).tolist(), 22)
+    """tests/leg2_rule.py boundary_lengths: groups at the edges of both widths, a ragged last tile of 20 rows."""
+    return from_lengths(boundary_lengths(), 22)
 
 
 def heavy_row_graph():
-    """One row of 400 entries among rows of <= 8: its 32-row block is cut into pieces (tuning balance), which shifts the
-    groups of four tiles behind it off the 128-row grid; the groups of cut tiles take the general path, their neighbours
-    the short one."""
-    rng = np.random.default_rng(23)
-    lengths = rng.integers(0, 9, 700)
-    lengths[200] = 400
-    return from_lengths(lengths.astype(int).tolist(), 24)
-
-
-def tiles_of(rowptr, n, balance=2):
-    """api.hip build_tiles: 32-row blocks, those heavier than balance x the mean cut into halves."""
-    nnz = int(rowptr[-1])
-    if nnz <= 0:
-        return []
-    nblk = (n + 31) // 32
-    limit = max(balance * ((nnz + nblk - 1) // nblk), 256)
-    out = []
-    for b in range(nblk):
-        stack = [(b * 32, min(n, b * 32 + 32))]
-        while stack:
-            lo, hi = stack.pop()
-            if rowptr[hi] - rowptr[lo] <= limit or hi - lo <= 1:
-                out.append(lo)
-            else:
-                mid = lo + (hi - lo + 1) // 2
-                stack.append((mid, hi))
-                stack.append((lo, mid))
-    out.append(n)
-    return out
-
-
-def short_groups(lengths, width):
-    """The rule: a group of four consecutive tiles is short when each tile is a whole 32-row block (or the ragged last one)
-    and no row of it has more than `width` entries."""
-    n = len(lengths)
-    if width == 0 or n < 64:
-        return 0
-    rowptr = np.concatenate([[0], np.cumsum(lengths)])
-    t = tiles_of(rowptr, n)
-    n_tiles = len(t) - 1
-    count = 0
-    for k in range((n_tiles + 3) // 4):
-        ok = True
-        for i in range(4 * k, min(4 * k + 4, n_tiles)):
-            lo, hi = t[i], t[i + 1]
-            ok = ok and lo % 32 == 0 and hi == min(n, lo + 32) and (hi == lo or max(lengths[lo:hi]) <= width)
-        count += int(ok)
-    return count
+    """tests/leg2_rule.py heavy_row_lengths: one row of 400 entries among rows of <= 8."""
+    return from_lengths(heavy_row_lengths(), 24)
 
 
 def oracle(csr, scale, evidence, apriori, lbd, coef, updates=UPDATES):

@@ -197,3 +197,86 @@ def test_biregular_graph():
     assert set(df.groupby("user").size()) == {2} and set(df.groupby("item").size()) == {4}
     *_, G12, G21 = O.bipartite_graph(df)
     assert np.array_equal(np.unique(G12), [0, 0.5]) and np.array_equal(np.unique(G21), [0, 0.25])
+
+
+# ---- the graphs built for leg 2's short path (tests/test_gpu_exact_short.py) ----------------------------------------
+def test_short_rule_over_the_graph_list():
+    """The rule of tests/leg2_rule.py on every graph: some groups short at 8, strictly more at 16; every graph with more than
+    one group keeps a group that is NOT short at 16 (the general path runs in the same launch), except the equal-length
+    ones; n = 64 is one short group, n = 63 has no image; the lengths are the ones the docstring of short_lengths names."""
+    from tests import leg2_rule as R
+    L = X.short_lengths()
+    assert set(L) == set(X.SHORT_GRAPHS)
+    rule = {name: {w: R.short_groups(L[name][0], w) for w in X.SHORT_WIDTHS} for name in L}
+    print(rule)
+    assert all(r[0] == 0 for r in rule.values())
+    assert 0 < sum(r[8] for r in rule.values()) < sum(r[16] for r in rule.values())
+    for name, (lengths, _) in L.items():
+        groups = R.tile_groups(lengths)
+        assert len(lengths) <= 700 and rule[name][8] <= rule[name][16] <= groups
+        if name not in X.SHORT_EQUAL and groups > 1:
+            assert rule[name][16] < groups, name
+    assert [len(L[k][0]) for k in ("boundary", "ragged21", "ragged1")] == [660, 661, 641]
+    for name in ("boundary", "ragged21", "ragged1"):
+        assert rule[name] == {0: 0, 8: 3, 16: 5} and R.tile_groups(L[name][0]) == 6
+        assert R.group_flags(L[name][0], 8) == [True, False, False, False, True, True]
+        assert R.group_flags(L[name][0], 16) == [True, True, True, False, True, True]
+        assert {0, 8, 9, 16, 17} <= set(L[name][0]) and not any(L[name][0][64:96])      # ... and a wholly empty tile
+    assert rule["n64"] == {0: 0, 8: 1, 16: 1} and R.tile_groups(L["n64"][0]) == 1
+    assert rule["n63"] == {0: 0, 8: 0, 16: 0}
+    assert R.group_flags(L["n129"][0], 8) == R.group_flags(L["n129"][0], 16) == [False, True]
+    heavy = L["heavy_row"][0]
+    tiles = R.tiles_of(np.concatenate([[0], np.cumsum(heavy)]), len(heavy))
+    assert max(heavy) == X.HEAVY_ROW == 400 and len(tiles) - 1 > (len(heavy) + 31) // 32       # the block is cut
+    assert any(t % 32 for t in tiles[:-1]) and 0 < rule["heavy_row"][8] == rule["heavy_row"][16] < R.tile_groups(heavy)
+    assert rule["equal8"] == {0: 0, 8: 2, 16: 2} and rule["equal16"] == {0: 0, 8: 0, 16: 2}
+    assert set(L["equal8"][0]) == {8} and set(L["equal16"][0]) == {16}
+
+
+@pytest.mark.parametrize("name", X.SHORT_GRAPHS)
+@pytest.mark.parametrize("variant", ["plain", "evidence", "all"])
+def test_short_cases_are_summable_and_every_row_holds_a_planted_tie(name, variant):
+    csr, sym, counts, prior, lbd, want, lengths = X.short_case(name, variant)
+    n = csr.n_rows
+    assert np.array_equal(np.diff(csr.rowptr), lengths) and X.is_pow2_or_zero(csr.rowscale)
+    bits = 24 - X.HEADROOM[variant]
+    assert 0 < sym.used1 < 1 and 0 < sym.used2 < 1
+    P = X.pattern(csr)
+    assert int(np.asarray(np.abs(sym.KT) @ P.T).max()) < 2 ** bits          # leg 2's condition, once more, in integers
+    assert np.array_equal(sym.Tt, X.product64(csr, sym.S).T) and np.array_equal(want, want.T)
+    assert np.array_equal(np.diag(want), np.ones(n))
+    places = X.tie_places_every_row(n)
+    assert len(places) == len(set(places)) and 4 * n <= len(places) + 4 * 32 and len(places) <= 5 * n
+    for a in (0, n // 2, n - 1):
+        b0 = a // 32 * 32
+        assert {(a, a), (a, b0), (a, min(n - 1, b0 + 31)), (a, n - 1), (a, (7 * a + 3) % n)} <= set(places)
+    want32, p, q = X.short_planted(name, variant)
+    assert set(p.kinds) == {"on", "above", "below"} and set(q.kinds) == {"on", "below"}
+    d = np.abs(want32.astype(np.float64) - p.previous.astype(np.float64))
+    assert np.array_equal(p.previous, p.previous.T) and (d > 0).any(axis=1).all()       # every row holds a planted tie
+    assert p.count == int((d > X.SHORT_EPS).sum()) > 0
+    assert int((d >= X.SHORT_EPS).sum()) > p.count                                     # a >= would count the ties
+    # some planted differences count and some do not
+    moved = (d > X.SHORT_EPS).any(axis=1)
+    quiet = ((d > 0) & (d <= X.SHORT_EPS)).any(axis=1)
+    assert moved.any() and quiet.any()
+    dq = np.abs(want32.astype(np.float64) - q.previous.astype(np.float64))
+    assert q.count == 0 and not (dq > X.SHORT_EPS).any() and (dq > 0).any(axis=1).all()
+
+
+def test_exact_updates_on_the_graph_with_rows_of_16():
+    """regular_graph(520, 16), the whole loop that is general at leg2_short = 8 and short at 16 (tests/test_gpu_exact_fits.py):
+    2 exact updates plain (enough for a tie), 1 for SimRank++ (too few: that class is left out there)."""
+    df = X.regular_graph(520, 16, seed=520 + 16)
+    _, G = O.directed_graph(df)
+    assert np.array_equal(np.unique(G), [0.0, 1.0 / 16]) and np.array_equal((G != 0).sum(axis=1), np.full(520, 16))
+    plain = X.exact_updates(G, 0.5)
+    assert (plain.updates, plain.grid_bits) == (2, 18) and plain.bits < 24
+    assert X.exact_updates(G, 0.5, O.evidence(G), limit=8).updates == 1
+    its = X.oracle_iterates(G, 0.5, None, 2)
+    U, eps, step = X.tie_eps(its)
+    assert U == 2 and np.any(np.abs(its[1] - its[0]) == eps)
+    S, k = O.iterate_directed(G, 0.5, U, eps)
+    assert k == 1 and np.array_equal(S, its[1])
+    S, k = O.iterate_directed(G, 0.5, U, eps - step)
+    assert k is None and np.array_equal(S, its[2])

@@ -7,6 +7,8 @@ plan stepped update by update, virtual ranks in the full and the half form with 
 the C ABI, float64 storage, fp16 storage and the fp16 wire — must return the oracle's frame exactly, with the oracle's
 `converged_at`.  Ties: with eps = a difference that occurs in the run, the loop stops where the oracle's strict > stops.
 SimRank.py:124-141, :346-363 and the two-matrix loop :280-302."""
+import contextlib
+
 import numpy as np
 import pytest
 
@@ -15,12 +17,39 @@ from oracle import simrank_oracle as O
 from simrank_amd import ingest
 from simrank_amd.driver import LocalWorld
 from tests import exact as X
+from tests.leg2_rule import short_groups
 
 pytestmark = pytest.mark.gpu
 
 GRAPHS = [(300, 2), (300, 4), (1031, 4), (2100, 8)]
 HALF_FORM = (512, 4)            # a node count the half form of a sharded leg 2 takes (a multiple of 32 x ranks) at 2, 4, 8 ranks
 TINY = 1e-30                    # an eps no difference of these runs is below, but zero
+# Leg 2's short path (tuning "leg2_short"): every row of regular_graph(n, d) has d entries and every tile is whole, so every
+# group of four tiles is short at every width >= d and none below.  GRAPHS (d <= 8) are short at 8 and at 16; the graph with
+# d = 16 is general at 8 and short at 16, the one whole loop in which the two widths differ (plain SimRank only: its exact
+# updates are 2 plain and 1 for SimRank++, too few for these tests).
+LEG2_WIDTHS = (0, 8, 16)
+SHORT_AT_16_ONLY = (520, 16)
+# the two-launch upper-triangle leg 2 on the plain pattern, whatever a plan would choose by itself on these graphs (the
+# one-launch leg 2 and the dense part are other kernels): as BASE of tests/leg2_short_worker.py
+TWO_LAUNCH = dict(fuse_sym=0, dense_sym=0, ids16=1, restrict_support=0, balance=2)
+
+
+@contextlib.contextmanager
+def leg2_width(ops, width):
+    """The process-wide tuning with the two-launch leg 2 forced and leg2_short = width; restored."""
+    kw = dict(TWO_LAUNCH, leg2_short=width)
+    saved = {k: ops.get_tuning(k) for k in kw}
+    ops.set_tuning(**kw)
+    try:
+        yield
+    finally:
+        ops.set_tuning(**saved)
+
+
+def leg2_rule(c, width):
+    """Short groups of regular_graph(n, d) at `width`, from the rule in NumPy (the order of equal-length rows is immaterial)."""
+    return short_groups([c.d] * c.n, width)
 
 
 class Case:
@@ -111,12 +140,7 @@ def test_fit_is_the_oracle(n, d, cls, mode):
         assert np.array_equal(np.asarray(est.Evidence), c.evidence())
 
 
-@pytest.mark.parametrize("n,d", GRAPHS)
-@pytest.mark.parametrize("cls", ["SimRank", "SimRankPP"])
-def test_fit_stops_on_a_tie_where_the_oracle_stops(n, d, cls):
-    """eps = max |S_{U-1} - S_{U-2}|: the test at loop index U - 1 passes only under strict >; one grid step less and it
-    does not pass, and the loop applies all U updates."""
-    c = case(n, d)
+def _stops_on_a_tie(c, cls):
     pp = cls == "SimRankPP"
     U, eps, step = X.tie_eps(c.iterates(pp, c.updates(pp)))
     S, k = c.oracle(pp, U, eps)
@@ -131,17 +155,43 @@ def test_fit_stops_on_a_tie_where_the_oracle_stops(n, d, cls):
     same_frame(got, S, c.labels)
 
 
-# ---- the plan, update by update ------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,d", GRAPHS)
-@pytest.mark.parametrize("pp", [False, True])
-@pytest.mark.parametrize("identity_leg1", ["1", "0"])
-def test_plan_stepped_update_by_update(ops, monkeypatch, n, d, pp, identity_leg1):
-    """simrank_plan_step: after every update the oracle's iterate, and the count of that update on a tie — eps = the largest
-    difference of the update but one grid step: exactly the elements that moved by the largest difference count."""
-    from simrank_amd.engine import Plan
-    monkeypatch.setenv("SIMRANK_IDENTITY_LEG1", identity_leg1)
+@pytest.mark.parametrize("cls", ["SimRank", "SimRankPP"])
+def test_fit_stops_on_a_tie_where_the_oracle_stops(n, d, cls):
+    """eps = max |S_{U-1} - S_{U-2}|: the test at loop index U - 1 passes only under strict >; one grid step less and it
+    does not pass, and the loop applies all U updates."""
+    _stops_on_a_tie(case(n, d), cls)
+
+
+@pytest.mark.parametrize("n,d", GRAPHS + [SHORT_AT_16_ONLY])
+@pytest.mark.parametrize("width", LEG2_WIDTHS)
+def test_fit_stops_on_a_tie_on_each_path_of_leg2(ops, monkeypatch, n, d, width):
+    """The same (SimRank) with the two-launch leg 2 forced and leg2_short = 0, 8, 16: the general path, and the short path
+    where the rule says so — read from the plan of every fit ("leg2_short_groups" after its run)."""
+    from simrank_amd import cplan
     c = case(n, d)
+    assert c.updates(False) >= 2
+    seen = []
+    run = cplan.PlanSolver.run
+
+    def spy(self, *a, **kw):
+        out = run(self, *a, **kw)
+        seen.append(self.plan.get("leg2_short_groups"))
+        return out
+    monkeypatch.setattr(cplan.PlanSolver, "run", spy)
+    with leg2_width(ops, width):
+        _stops_on_a_tie(c, "SimRank")
+    rule = leg2_rule(c, width)
+    assert seen == [rule, rule] and rule == (0 if width < d else ((n + 31) // 32 + 3) // 4), (seen, rule)
+
+
+# ---- the plan, update by update ------------------------------------------------------------------------------------
+def _stepped(ops, c, pp, groups=None):
+    """simrank_plan_step, update by update; `groups`: what "leg2_short_groups" must say after every update."""
+    from simrank_amd.engine import Plan
+    n = c.n
     U = c.updates(pp)
+    assert U >= 2
     its = c.iterates(pp, U)
     nodes, csr = ingest.directed(c.df, False, "from", "to", "weight")
     assert nodes == c.labels
@@ -163,9 +213,35 @@ def test_plan_stepped_update_by_update(ops, monkeypatch, n, d, pp, identity_leg1
                 want = int((diff > eps).sum())
                 assert want == int((diff == top).sum())
             assert plan.step(eps, exact_count=True) == want, (u, eps)
+            assert groups is None or plan.get("leg2_short_groups") == groups, (u, plan.get("leg2_short_groups"), groups)
             assert np.array_equal(plan.result(), its[u]), u
     finally:
         plan.free()
+
+
+@pytest.mark.parametrize("n,d", GRAPHS)
+@pytest.mark.parametrize("pp", [False, True])
+@pytest.mark.parametrize("identity_leg1", ["1", "0"])
+def test_plan_stepped_update_by_update(ops, monkeypatch, n, d, pp, identity_leg1):
+    """simrank_plan_step: after every update the oracle's iterate, and the count of that update on a tie — eps = the largest
+    difference of the update but one grid step: exactly the elements that moved by the largest difference count."""
+    monkeypatch.setenv("SIMRANK_IDENTITY_LEG1", identity_leg1)
+    _stepped(ops, case(n, d), pp)
+
+
+@pytest.mark.parametrize("n,d,pp", [(n, d, pp) for n, d in GRAPHS for pp in (False, True)] + [SHORT_AT_16_ONLY + (False,)])
+@pytest.mark.parametrize("width", LEG2_WIDTHS)
+def test_plan_stepped_on_each_path_of_leg2(ops, monkeypatch, n, d, pp, width):
+    """The same with the two-launch upper-triangle leg 2 forced (TWO_LAUNCH: a plan may choose the one-launch leg 2 or the
+    dense part by itself, and the rule speaks about neither) and leg2_short = 0, 8, 16: at 0 the general gather3 kSym leg
+    runs the whole loop, at 8 and 16 every group is short on GRAPHS, on the d = 16 graph at 16 only.  After every update the
+    plan's "leg2_short_groups" is the rule's number, the iterate and the count on a tie are the oracle's."""
+    monkeypatch.setenv("SIMRANK_IDENTITY_LEG1", "1")
+    c = case(n, d)
+    rule = leg2_rule(c, width)
+    assert rule == (0 if width < d else ((n + 31) // 32 + 3) // 4)            # every group of four 32-row tiles, or none
+    with leg2_width(ops, width):
+        _stepped(ops, c, pp, groups=rule)
 
 
 # ---- virtual ranks --------------------------------------------------------------------------------------------------

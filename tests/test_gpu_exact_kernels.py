@@ -16,12 +16,13 @@ import pytest
 
 from simrank_amd.ingest import CSR
 from tests import exact as X
+from tests.leg2_rule import short_groups
 from tests.test_gpu_kernels import dense64
 
 pytestmark = pytest.mark.gpu
 
 KNOBS = ("panel", "fuse", "fuse_min", "fuse_steps", "fuse_unit", "fuse_group", "fuse_shards", "fuse_rows", "fuse_order",
-         "fuse_sym", "ids16", "dense_min", "dense_cols", "dense_sym", "lean", "triangle", "balance", "addr32")
+         "fuse_sym", "ids16", "dense_min", "dense_cols", "dense_sym", "lean", "triangle", "balance", "addr32", "leg2_short")
 
 
 @pytest.fixture(scope="module")
@@ -359,19 +360,22 @@ def _leg2(ops, g, tt32, n, blocked, symmetric, counts, prior, lbd, prev, **kw):
     return got, exact, some
 
 
-def _check_counts(run, want32, what):
+def _check_counts(run, want32, what, planted=None):
     """`run(previous)` -> (result, exact count, count_any count) against planted ties: the reference's strict > count; then
-    with nothing above eps: zero, both forms."""
+    with nothing above eps: zero, both forms.  `planted`: (all three kinds, "on" and "below" only) of X.plant_previous made
+    elsewhere from the same reference at places of the caller's (default: here, at X.tie_places)."""
     n, L = want32.shape
-    sym = n == L and np.array_equal(want32, want32.T)
-    places = X.tie_places(n, L)
-    p = X.plant_previous(want32, EPS, places, symmetric=sym)
+    if planted is None:
+        sym = n == L and np.array_equal(want32, want32.T)
+        places = X.tie_places(n, L)
+        planted = (X.plant_previous(want32, EPS, places, symmetric=sym),
+                   X.plant_previous(want32, EPS, places, symmetric=sym, only=("on", "below")))
+    p, q = planted
     assert p.count > 0
     got, exact, some = run(p.previous)
     equal_bits(got, want32, what)
-    assert exact == p.count, (what, exact, p.count, p.kinds)
+    assert exact == p.count, (what, exact, p.count, p.kinds[:24])
     assert 0 < some <= exact, (what, some, exact)
-    q = X.plant_previous(want32, EPS, places, symmetric=sym, only=("on", "below"))
     assert q.count == 0
     got, exact, some = run(q.previous)
     equal_bits(got, want32, what)
@@ -397,13 +401,22 @@ def test_leg2_every_form_gives_the_reference_bits_and_the_strict_count(ops, n, v
              ("blocked one-launch, split blocks", dict(fuse_sym=1, fuse_min=3, fuse_steps=2, fuse_unit=4, fuse_rows=400), True, True),
              ("blocked one-launch, fuse_group 1", dict(fuse_sym=1, fuse_group=1), True, True),
              ("blocked two-launch (gather3 kSym)", dict(fuse_sym=0), True, True),
+             # ... and the same leg saying which of its two paths it runs (dense_sym=0: no dense part whatever the
+             # pattern, so that the launch is the one the rule of tests/leg2_rule.py speaks about)
+             ("blocked two-launch, general path (gather3 kSym)", dict(fuse_sym=0, dense_sym=0, balance=2, leg2_short=0), True, True),
+             ("blocked two-launch, short path (gather3 kSym SHORT)", dict(fuse_sym=0, dense_sym=0, balance=2, leg2_short=16), True, True),
              ("blocked full form", dict(fuse_sym=0), True, False)]
+    lengths = np.diff(csr.rowptr).tolist()
     for what, kw, blocked, symmetric in forms:
         with knobs(ops, **kw):
             g = ops.graph(csr)
             if "one-launch" in what:
                 assert ops.fused_stats(g)[1] > 0 and ops.graph_get(g, "fused_ids16") == kw.get("ids16", 1)
             _check_counts(lambda prev: _leg2(ops, g, tt32, n, blocked, symmetric, counts, prior, lbd, prev), want32, what)
+            if "leg2_short" in kw:
+                rule = short_groups(lengths, kw["leg2_short"])
+                assert ops.graph_get(g, "leg2_short_groups") == rule == ops.graph_get(g, "leg2_short_taken"), (what, rule)
+                assert kw["leg2_short"] or rule == 0
     # an ld off the 16-byte grid: the scalar kernel (no triangle form there)
     with knobs(ops, fuse=0):
         g = ops.graph(csr)

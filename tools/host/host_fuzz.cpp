@@ -484,6 +484,10 @@ int main(int argc, char** argv) {
                       v == (g->fused ? int64_t(ids16 && c.K <= 65535) : int64_t(-1)), "graph_get fused_ids16 = %lld", (long long)v);
             CHECK(simrank_graph_get(g, "gather_ids16", &v) == SIMRANK_OK && v == int64_t(ids16 && g->col16 != nullptr),
                   "graph_get gather_ids16 = %lld", (long long)v);
+            // ... and the short image's groups as the graph holds them; no launch yet, so none taken
+            CHECK(simrank_graph_get(g, "leg2_short_groups", &v) == SIMRANK_OK && v == int64_t(g->short_groups) && v >= 0,
+                  "graph_get leg2_short_groups = %lld", (long long)v);
+            CHECK(simrank_graph_get(g, "leg2_short_taken", &v) == SIMRANK_OK && v == 0, "graph_get leg2_short_taken = %lld", (long long)v);
             v = -7;
             CHECK(simrank_graph_get(g, "no_such_key", &v) == SIMRANK_ERR_INVALID && v == -7 &&
                       strstr(simrank_last_error(), "no_such_key"), "graph_get: unknown key accepted");
