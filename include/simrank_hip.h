@@ -404,7 +404,8 @@ SIMRANK_API int simrank_graph_fused_stats(const simrank_graph* g, int64_t* n_ste
                                           int64_t* nnz_covered, int64_t* nnz_remainder);
 /* What a graph chose when it was built, by key: "fused_ids16" 1 | 0 the one-launch plan streams 16 | 32-bit ids (-1: the
  * graph has no such plan), "gather_ids16" 1 | 0 the gather kernel streams 16 | 32-bit ids, "leg2_short_groups" the groups
- * of four 32-row tiles in the short image built with the graph (tuning "leg2_short"; 0: no image).  One key says what the
+ * of four 32-row tiles in the short image built with the graph (tuning "leg2_short"; 0: no image), "ev_hubs" the hub columns
+ * whose pairs the evidence counts take on the matrix cores (tuning "ev_hub"; at most 4096, 0: no hub part).  One key says what the
  * LATEST launch did: "leg2_short_taken" the short groups that the latest simrank_spmm* call with an epilogue on this graph
  * ran on the short path (0 before any, and for every launch that is not the panel-blocked upper-triangle gather with
  * 16-bit ids, unrestricted, without a dense part).  SIMRANK_ERR_INVALID (with the message) for a NULL handle or an

@@ -818,6 +818,7 @@ int graph_create_with(const Tuning& tun, int64_t n_rows, int64_t n_cols, int64_t
         if (cand.size() > 4096) cand.resize(4096);
         if (cand.size() >= 8) {
             for (size_t h = 0; h < cand.size(); ++h) hubidx[size_t(cand[h])] = (int32_t)h;
+            g->ev_hub_cols = (int32_t)cand.size();
             g->ev_hubs = (int32_t)((cand.size() + 31) / 32 * 32);
         }
     }
@@ -1118,6 +1119,7 @@ int simrank_graph_get(const simrank_graph* g, const char* key, int64_t* value) {
     else if (!strcmp(key, "gather_ids16")) *value = (g->col16 && g->tun.ids16) ? 1 : 0;
     else if (!strcmp(key, "leg2_short_groups")) *value = g->short_groups;
     else if (!strcmp(key, "leg2_short_taken")) *value = g->leg2_short_taken;
+    else if (!strcmp(key, "ev_hubs")) *value = g->ev_hub_cols;
     else SR_REQUIRE(false, "unknown graph key '%s'", key);
     return SIMRANK_OK;
 }

@@ -406,6 +406,7 @@ struct simrank_graph {
     int32_t* t_pos = nullptr;     // [nnz]       slot of CSR entry j in its column's list (live rows only)
     int32_t* ev_hubidx = nullptr; // [n_cols]    index of a HUB column in the 0/1 image of the evidence counts, -1: none
     int32_t ev_hubs = 0;          // columns of that image (a multiple of 32; 0: no hub columns)
+    int32_t ev_hub_cols = 0;      // hub columns chosen (at most 4096; ev_hubs is this rounded up to 32): simrank_graph_get "ev_hubs"
     uint8_t* ev_hub_image = nullptr;  // [rows padded to 128][ev_hubs] the image itself, built at the first evidence call
     void* ev_hub_ready = nullptr;     // hipEvent_t recorded behind that build: an evidence call on ANOTHER stream waits for it
     int32_t max_row_nnz = 0;

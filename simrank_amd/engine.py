@@ -1269,8 +1269,8 @@ class HipOps:
 
     def graph_get(self, g, key: str) -> int:
         """What a graph (a ``Graph``, or the handle of a plan's graph) chose when it was built (simrank_graph_get):
-        "fused_ids16" (-1: no one-launch plan), "gather_ids16", "leg2_short_groups" (groups in its short image), and what
-        its latest launch with an epilogue did: "leg2_short_taken" (short groups that ran the short path)."""
+        "fused_ids16" (-1: no one-launch plan), "gather_ids16", "leg2_short_groups" (groups in its short image), "ev_hubs" (hub
+        columns of its evidence counts, 0: none), and what its latest launch with an epilogue did: "leg2_short_taken" (short groups that ran the short path)."""
         v = C.c_int64(0)
         check(self.lib.simrank_graph_get(getattr(g, "handle", g), key.encode(), C.byref(v)), f"simrank_graph_get({key})")
         return v.value

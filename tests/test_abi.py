@@ -86,7 +86,7 @@ def test_choice_getters_refuse_a_null_handle_and_an_unknown_key(name):
     lib = _lib.load()
     fn = getattr(lib, name)
     head = (None, 1) if name == "simrank_biplan_get" else (None,)
-    keys = [b"restrict_support"] if _GETTERS[name] == "plan" else [b"fused_ids16", b"gather_ids16", b"leg2_short_groups", b"leg2_short_taken"]
+    keys = [b"restrict_support"] if _GETTERS[name] == "plan" else [b"fused_ids16", b"gather_ids16", b"leg2_short_groups", b"leg2_short_taken", b"ev_hubs"]
     for key in keys + [b"no_such_key"]:
         v = ctypes.c_int64(-7)
         assert fn(*head, key, ctypes.byref(v)) == -1

@@ -488,6 +488,9 @@ int main(int argc, char** argv) {
             CHECK(simrank_graph_get(g, "leg2_short_groups", &v) == SIMRANK_OK && v == int64_t(g->short_groups) && v >= 0,
                   "graph_get leg2_short_groups = %lld", (long long)v);
             CHECK(simrank_graph_get(g, "leg2_short_taken", &v) == SIMRANK_OK && v == 0, "graph_get leg2_short_taken = %lld", (long long)v);
+            // ... and the hub columns of the evidence counts: the number chosen, of which the image's width is the next multiple of 32
+            CHECK(simrank_graph_get(g, "ev_hubs", &v) == SIMRANK_OK && v == int64_t(g->ev_hub_cols) && (v == 0 || (v >= 8 && v <= 4096)) &&
+                      int64_t(g->ev_hubs) == (v + 31) / 32 * 32, "graph_get ev_hubs = %lld", (long long)v);
             v = -7;
             CHECK(simrank_graph_get(g, "no_such_key", &v) == SIMRANK_ERR_INVALID && v == -7 &&
                       strstr(simrank_last_error(), "no_such_key"), "graph_get: unknown key accepted");
