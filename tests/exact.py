@@ -15,7 +15,9 @@ No tolerance is involved anywhere: the float64 NumPy result cast to float32 is T
 exactly summable: what the upper-triangle forms need), `exact_epilogue` is the oracle's epilogue expression with a check
 that no intermediate of any association rounds in float32, `plant_previous` puts differences of exactly eps, eps + one step
 and eps - one step at chosen places, `regular_graph` / `exact_updates` give whole fits whose iterates stay exact;
-`short_lengths` / `short_case` / `tie_places_every_row` are the graphs, operands and tie places built for leg 2's short path.
+`short_lengths` / `short_case` / `tie_places_every_row` are the graphs, operands and tie places built for leg 2's short path;
+`loop_prior`, `pow2_degree_graph`, `matched_biregular_graph`, `prior_case` / `bi_prior_case` and `count_eps` are the priors,
+graphs, cached oracle iterates and counting eps of the whole loops with a prior (tests/test_gpu_exact_priors.py).
 """
 from collections import namedtuple
 
@@ -321,81 +323,207 @@ def biregular_graph(n1, n2, d1, seed):
     return df
 
 
+def matched_biregular_graph(n1, n2, d1, seed):
+    """Bipartite edge list with the degrees of biregular_graph (every user d1 items, every item d2 = n1 * d1 / n2 users) as a
+    union of d1 RANDOM matchings (user u's k-th item: perm_k[u] mod n2): no two nodes need share their whole neighbour list,
+    as the nodes of biregular_graph do in pairs — there W S W^T of an asymmetric S is symmetric wherever the evidence is
+    not zero, and an asymmetric prior on one side never reaches the other."""
+    d2 = n1 * d1 // n2
+    assert n1 % n2 == 0 and d1 & (d1 - 1) == 0 and d2 & (d2 - 1) == 0
+    rng = np.random.default_rng(seed)
+    for _ in range(100):
+        items = np.stack([rng.permutation(n1) % n2 for _ in range(d1)], axis=1)
+        if all(len(set(row)) == d1 for row in items.tolist()):
+            break
+    else:
+        raise AssertionError("no union of matchings without a repeated pair")
+    df = pd.DataFrame({"user": np.repeat(np.arange(n1, dtype=np.int64), d1), "item": items.ravel().astype(np.int64), "weight": 1.0})
+    assert set(df.groupby("user").size()) == {d1} and set(df.groupby("item").size()) == {d2}
+    return df
+
+
+def pow2_degree_graph(n, degrees, hubs, share, seed):
+    """Edge list (from, to, weight) without self loops or repeated edges in which every node's in-degree is a member of
+    `degrees` (powers of two, dealt evenly) and a fraction `share` of all references goes to the first `hubs` nodes, dealt
+    to them in turn: hub columns that many rows reference (dense sets for the matrix cores) beside rows of a few entries,
+    with row scales that are powers of two."""
+    assert all(d & (d - 1) == 0 and 0 < d < hubs for d in degrees) and 0 < hubs < n - max(degrees) and 0 <= share <= 1
+    rng = np.random.default_rng(seed)
+    deg = np.array([degrees[i % len(degrees)] for i in range(n)], dtype=np.int64)
+    rng.shuffle(deg)
+    src, dst, acc, taken, turn, waiting = [], [], 0.0, 0, 0, []
+    for v in range(n):
+        acc += share * deg[v]
+        h = int(np.floor(acc + 1e-9)) - taken            # (error diffusion: floor(share * references) go to hubs in all)
+        h = min(h, int(deg[v]))
+        taken += h
+        mine = []
+        while len(mine) < h:
+            if waiting and waiting[0] != v:
+                mine.append(waiting.pop(0))              # (a hub that was passed over as its own row: the next row takes it)
+                continue
+            u = turn % hubs
+            turn += 1
+            if u == v:
+                waiting.append(u)
+            else:
+                mine.append(u)
+        rest = rng.choice(n - hubs - (1 if v >= hubs else 0), size=int(deg[v]) - h, replace=False) + hubs
+        rest = rest + ((rest >= v) if v >= hubs else 0)
+        src += mine + rest.tolist()
+        dst += [v] * int(deg[v])
+    df = pd.DataFrame({"from": np.array(src, dtype=np.int64), "to": np.array(dst, dtype=np.int64), "weight": 1.0})
+    assert not df.duplicated(["from", "to"]).any() and not (df["from"] == df["to"]).any()
+    assert set(df.groupby("to").size()) <= set(degrees) and df["to"].nunique() == n
+    return df
+
+
+def loop_prior(n, bits, seed, symmetric, density=1.0, half=False):
+    """A prior for whole loops: float64 integers in [0, 2^bits) times 2^-bits, dense (`density` < 1: that share non-zero),
+    symmetric or — A[r, c] != A[c, r] for more than a quarter of the pairs — not.  The update overwrites the diagonal, so
+    it holds values that differ from 1 and from each other (2 + i: a kernel that lets one through shows it; `half`, for
+    fp16-held matrices, which take prior values below 4 only: 2 + i / 512, fp16 numbers also when held x 2^14)."""
+    rng = np.random.default_rng(seed)
+    k = rng.integers(0, 2 ** bits, size=(n, n), dtype=np.int64)
+    if density < 1.0:
+        k *= rng.random((n, n)) < density
+    if symmetric:
+        k = np.triu(k) + np.triu(k, 1).T
+    A = k.astype(np.float64) * 2.0 ** -bits
+    assert not half or n <= 1024
+    A[np.arange(n), np.arange(n)] = 2.0 + np.arange(n) * (2.0 ** -9 if half else 1.0)
+    assert np.array_equal(A.astype(np.float32).astype(np.float64), A)
+    differ = int((np.triu(A != A.T, 1)).sum())
+    if symmetric:
+        assert differ == 0
+    elif density == 1.0:
+        assert differ > n * (n - 1) // 2 // 4
+    else:
+        assert differ > 0
+    return A
+
+
 def lowbit_exp(a):
     """Exponent of the lowest set bit over all non-zero elements (float64 array); None when all are zero."""
     a = np.asarray(a, dtype=np.float64)
-    a = a[a != 0]
+    a = np.abs(a[a != 0])
     if a.size == 0:
         return None
-    m, e = np.frexp(np.abs(a))
-    mant = (m * 2.0 ** 53).astype(np.int64)              # exact: 53-bit integers
-    tz = np.zeros(mant.shape, dtype=np.int64)
+    word = np.ascontiguousarray(a).view(np.int64)        # (read off the bits: 53-bit integer mant x 2^(field - 1075))
+    field = word >> 52
+    assert field.min() > 0 and field.max() < 2047, "subnormal or non-finite"
+    mant = (word & ((1 << 52) - 1)) | (1 << 52)
     low = mant & -mant
-    tz = np.log2(low.astype(np.float64)).astype(np.int64)
-    return int((e.astype(np.int64) - 53 + tz).min())
+    tz = (low.astype(np.float64).view(np.int64) >> 52) - 1023          # log2 of a power of two, from its exponent field
+    return int((field - 1075 + tz).min())
 
 
 Exact = namedtuple("Exact", "updates grid_bits bits")
 
 
-def _one_update(W, S, C, E, mantissa):
-    """One update new = E * C * W S W^T (diag <- 1) with the bookkeeping of exact_updates: -> (new, -log2 grid, quotient) or
-    None when exactness in float64 itself cannot be vouched for."""
+def _one_update(W, S, C, E, mantissa, prior=None, lbd=None):
+    """One update new = E * C * W S W^T (diag <- 1) — with a prior (1 - lbd) * E * C * W S W^T + lbd * prior — with the
+    bookkeeping of exact_updates: -> (new, -log2 grid, quotient) or None when exactness in float64 itself cannot be vouched
+    for.  An iterate that is not symmetric (a prior that is not) is booked on S AND on S^T: the device gathers rows of
+    Tt = (W S)^T and then rows of its own product W . Tt, which is the TRANSPOSE of W S W^T (stored transposed); the oracle
+    sums W S first and (W S) W^T second.  The update itself is taken as (W (W S)^T)^T."""
     rs = W.max(axis=1)
     assert is_pow2_or_zero(rs) and np.array_equal(W, rs[:, None] * (W != 0))
     P = sp.csr_matrix((W != 0).astype(np.float64))       # (a few entries per row: the products below cost nothing)
     c_exp = lowbit_exp(np.float64(C))
     assert 2.0 ** c_exp == C, "C must be a power of two"
-    sums1 = P @ S                                        # leg 1, unscaled (exact in float64 while the quotient is below 2^53)
-    T = rs[:, None] * sums1
-    sums2 = P @ T.T
-    prod = rs[:, None] * sums2
+    terms, totals, prod = [], [], None
+    for X in ((S,) if np.array_equal(S, S.T) else (S, S.T)):
+        sums1 = P @ X                                    # leg 1, unscaled (exact in float64 while the quotient is below 2^53)
+        T = rs[:, None] * sums1
+        sums2 = P @ T.T
+        p = rs[:, None] * sums2                          # W . (W X)^T = (W X W^T)^T
+        terms += [X, sums1, T, sums2, p]
+        totals += [(P @ np.abs(X)).max(), (P @ np.abs(T.T)).max()]
+        if prod is None:
+            prod = p.T                                   # from X = S: W S W^T, the transpose of what the device's leg 2 sums
     new = C * prod
-    terms = [S, sums1, T, sums2, prod, new]
-    totals = [(P @ np.abs(S)).max(), (P @ np.abs(T.T)).max(), np.abs(new).max(), 1.0]
+    terms.append(new)
     if E is not None:
+        terms.append(prod * E)                           # (s * E: the other association of E * C * s)
         new = E * new
         terms.append(new)
+    floor = lowbit_exp(S) + 2 * lowbit_exp(rs) + c_exp + (lowbit_exp(E) if E is not None and E.any() else 0)
+    if prior is not None:
+        keep = np.float64(1 - lbd)
+        assert float(np.float32(keep)) == float(keep) and float(np.float32(1.0) - np.float32(lbd)) == float(keep)
+        assert float(np.float32(lbd)) == float(lbd)
+        # (the diagonal of the update is overwritten with 1: what the blend gives there is read by nobody and is not booked)
+        A = np.asarray(prior, dtype=np.float64).copy()
+        np.fill_diagonal(A, 0.0)
+        off = 1.0 - np.eye(A.shape[0])
+        a, b = keep * new, lbd * A
+        if E is not None:
+            terms += [keep * E, keep * E * C]
+            assert np.array_equal((1 - lbd) * E * C * prod, a)
+        terms += [keep * C * prod, a * off, b, (a + b) * off]
+        new = a + lbd * np.asarray(prior, dtype=np.float64)
+        floor += lowbit_exp(keep)
+        if b.any():
+            floor = min(floor, lowbit_exp(np.float64(lbd)) + lowbit_exp(A))
     np.fill_diagonal(new, 1.0)
+    totals += [np.abs(C * prod).max(), np.abs(new).max(), 1.0]
     # (a bound that does not rest on the float64 results themselves: sums stay on their operands' grid, every scale moves it
     # by its own exponent — below 2^53 the numbers above are exact, and the measured grid can be trusted)
-    floor = lowbit_exp(S) + 2 * lowbit_exp(rs) + c_exp + (lowbit_exp(E) if E is not None and E.any() else 0)
     if max(totals) / 2.0 ** floor >= 2.0 ** 53:
         return None
     grid = floor if mantissa >= 53 else min(x for x in (lowbit_exp(t) for t in terms) if x is not None)
     return new, -grid, max(totals) / 2.0 ** grid
 
 
-def exact_updates(W, C=0.5, E=None, mantissa=24, limit=24):
+def _is_oracle_update(W, S, C, E, prior, lbd, new):
+    from oracle import simrank_oracle as O
+    want = O.update(W, S, C, E, prior, lbd) if prior is not None else O.update(W, S, C, E)
+    assert np.array_equal(new, want), "the booked update is not the oracle's, bit for bit"
+
+
+def exact_updates(W, C=0.5, E=None, mantissa=24, limit=24, prior=None, lbd=None):
     """How many updates of S' = E * C * W S W^T (diag <- 1) from S = I stay exact in a format of `mantissa` bits: after each
     update the coarsest common grid of the terms of both legs and of the epilogue (the lowest set bit over all non-zero
     terms: the elements of S, of W S unscaled and scaled, of C * prod, E * C * prod) divides the largest total (the largest
     sum of magnitudes a row of either leg can reach, the largest element); the count stops before that quotient reaches
-    2^mantissa.  -> (updates, -log2 of the grid at the last exact update, bits of the quotient there)."""
+    2^mantissa.  -> (updates, -log2 of the grid at the last exact update, bits of the quotient there).
+    `prior`, `lbd`: the update is (1 - lbd) * E * C * W S W^T + lbd * prior (oracle.update; E may be None: a plan without
+    evidence); the terms gain (1 - lbd) * E, (1 - lbd) * E * C, (1 - lbd) * x, lbd * prior and the blend, an iterate that is
+    not symmetric is booked on itself and on its transpose (_one_update), and every counted update is asserted to be
+    oracle.update's result bit for bit."""
     W = np.asarray(W, dtype=np.float64)
     S = np.eye(W.shape[0])
     last = Exact(0, 0, 0)
     for u in range(1, limit + 1):
-        r = _one_update(W, S, C, E, mantissa)
+        r = _one_update(W, S, C, E, mantissa, prior, lbd)
         if r is None or r[2] >= 2.0 ** mantissa:
             break
+        if prior is not None:
+            _is_oracle_update(W, S, C, E if E is not None else 1.0, prior, lbd, r[0])
         S = r[0]
         last = Exact(u, r[1], int(np.ceil(np.log2(r[2]))))
     return last
 
 
-def exact_updates_bipartite(W12, W21, C=0.5, E1=None, E2=None, mantissa=24, limit=24):
-    """The same count for the two-matrix loop (S1 from S2, then S2 from the new S1): both half-updates must stay exact."""
+def exact_updates_bipartite(W12, W21, C=0.5, E1=None, E2=None, mantissa=24, limit=24, prior1=None, prior2=None,
+                            lbd1=None, lbd2=None):
+    """The same count for the two-matrix loop (S1 from S2, then S2 from the new S1): both half-updates must stay exact.
+    `prior1`, `prior2` (both or neither) with `lbd1`, `lbd2`: the priors of the two groups, as in exact_updates."""
     W12, W21 = np.asarray(W12, dtype=np.float64), np.asarray(W21, dtype=np.float64)
+    assert (prior1 is None) == (prior2 is None)
     S2 = np.eye(W21.shape[0])
     last = Exact(0, 0, 0)
     for u in range(1, limit + 1):
-        r1 = _one_update(W12, S2, C, E1, mantissa)
+        r1 = _one_update(W12, S2, C, E1, mantissa, prior1, lbd1)
         if r1 is None or r1[2] >= 2.0 ** mantissa:
             break
-        r2 = _one_update(W21, r1[0], C, E2, mantissa)
+        r2 = _one_update(W21, r1[0], C, E2, mantissa, prior2, lbd2)
         if r2 is None or r2[2] >= 2.0 ** mantissa:
             break
+        if prior1 is not None:
+            _is_oracle_update(W12, S2, C, E1 if E1 is not None else 1.0, prior1, lbd1, r1[0])
+            _is_oracle_update(W21, r1[0], C, E2 if E2 is not None else 1.0, prior2, lbd2, r2[0])
         S2 = r2[0]
         last = Exact(u, max(r1[1], r2[1]), int(np.ceil(np.log2(max(r1[2], r2[2])))))
     return last
@@ -408,6 +536,149 @@ def oracle_iterates(W, C, E, updates):
     for _ in range(updates):
         out.append(O.update(W, out[-1], C, E))
     return out
+
+
+class PriorCase:
+    """A directed graph with a prior: the oracle's matrices and (lazily, once) the exact update count and the oracle's
+    iterates of (1 - lbd) * E * C * W S W^T + lbd * A with C = 0.5 (tests/test_exact_cpu.py, tests/test_gpu_exact_priors.py).
+    `evidence=False`: the plan-level loop without the evidence factor (simrank_plan_options allows it).  Nobody writes to
+    what this holds."""
+
+    def __init__(self, name, df, symmetric, lbd, bits=2, evidence=True, mantissa=24, limit=8):
+        from oracle import simrank_oracle as O
+        self.name, self.df, self.symmetric, self.lbd, self.bits = name, df, symmetric, lbd, bits
+        self.mantissa, self.limit = mantissa, limit
+        self.labels, self.G = O.directed_graph(df)
+        self.n = len(self.labels)
+        assert self.labels == list(range(self.n))
+        assert np.array_equal(O.weight(self.G), self.G)   # spread exactly 1, or 0 and 1 entries in a row: W is G
+        self.E = O.evidence(self.G) if evidence else None
+        self.A = loop_prior(self.n, bits, seed=self.n + bits + (0 if symmetric else 1), symmetric=symmetric,
+                            half=mantissa == 11)
+        self._exact, self._its = None, [np.eye(self.n)]
+
+    def exact(self):
+        if self._exact is None:
+            self._exact = exact_updates(self.G, 0.5, self.E, mantissa=self.mantissa, limit=self.limit, prior=self.A,
+                                        lbd=self.lbd)
+            print(f"{self.name} {'symmetric' if self.symmetric else 'asymmetric'} {self.bits}-bit prior, lbd {self.lbd}, "
+                  f"mantissa {self.mantissa}{'' if self.E is not None else ', no evidence'}: {self._exact}")
+        return self._exact
+
+    updates = property(lambda self: self.exact().updates)
+
+    def iterates(self, updates=None):
+        from oracle import simrank_oracle as O
+        updates = self.updates if updates is None else updates
+        while len(self._its) <= updates:
+            self._its.append(O.update(self.G, self._its[-1], 0.5, 1.0 if self.E is None else self.E, self.A, self.lbd))
+        return self._its[:updates + 1]
+
+    def oracle(self, iterations, eps):
+        """(S, k) of oracle.iterate_directed with the prior, from the cached iterates."""
+        from oracle import simrank_oracle as O
+        its = self.iterates(iterations)
+        old = np.zeros((self.n, self.n))
+        for k in range(iterations):
+            if O.converged(old, its[k], eps):
+                return its[k], k
+            old = its[k]
+        return its[iterations], None
+
+
+# the cases of tests/test_gpu_exact_priors.py (here, so that tests/test_exact_cpu.py pins every one of them)
+PRIOR_GRAPHS = [("regular", 300, 2), ("regular", 1031, 4), ("regular", 2100, 2), ("regular", 2100, 4)]
+PRIOR_RANK_GRAPHS = [("regular", 512, 4), ("regular", 1031, 4)]     # 512: the half form of a sharded leg 2 at 2, 4, 8 ranks
+PRIOR_LBD = (0.5, 0.25)
+HUB_GRAPHS = [("hubs", 1031, (1, 2, 4, 8)), ("hubs", 1031, (2, 4))]
+# rows of 2 and of 4 entries in a shuffled order, WITH evidence (2 exact updates; 1 with degrees up to 8): the graph on which
+# the solver's ascending-length order is a real permutation, so that a plan's upload permutes the prior
+MIXED_GRAPH = ("hubs", 1031, (2, 4))
+PRIOR_F64 = [("regular", 300, 2), ("regular", 1031, 4)]
+PRIOR_FP16 = [("regular", 300, 2), ("regular", 512, 2)]            # (a 1-bit prior; (1031, 4) has ONE exact update at 11 bits)
+# (n1, n2, d1, lbd, matched): biregular_graph(384, 192, 2) has 1 exact update with priors, and so has every graph here at
+# lbd 0.25 but the one with d1 = 1; matched_biregular_graph: the one in which an asymmetric prior reaches the other side
+BI_PRIOR = [(256, 256, 2, 0.5, False), (384, 192, 1, 0.5, False), (384, 192, 1, 0.25, False), (384, 384, 2, 0.5, True)]
+BI_PRIOR_KINDS = [(True, True), (False, True), (True, False)]     # both symmetric, prior 1 asymmetric alone, prior 2 alone
+_graphs, _prior_cases = {}, {}
+
+
+def loop_graph(key):
+    """("regular", n, d) -> regular_graph(n, d, n + d); ("hubs", n, degrees) -> pow2_degree_graph(n, degrees, 48, 0.5, n); once."""
+    if key not in _graphs:
+        kind, n, d = key
+        _graphs[key] = regular_graph(n, d, seed=n + d) if kind == "regular" else pow2_degree_graph(n, d, 48, 0.5, seed=n)
+    return _graphs[key]
+
+
+def prior_case(graph, symmetric, lbd, bits=2, evidence=True, mantissa=24):
+    """The PriorCase of loop_graph(graph), built once per argument list and shared."""
+    key = (graph, symmetric, lbd, bits, evidence, mantissa)
+    if key not in _prior_cases:
+        name = f"{graph[0]}_graph{graph[1:]}"
+        # (the loop limit: 8 updates, 10 in float64; 4 from 2000 nodes on, where the oracle's dense update is the slowest
+        # part of every test that leans on it)
+        limit = 4 if graph[1] >= 2000 else 8 if mantissa < 53 else 10
+        _prior_cases[key] = PriorCase(name, loop_graph(graph), symmetric, lbd, bits, evidence, mantissa, limit=limit)
+    return _prior_cases[key]
+
+
+class BiPriorCase:
+    """biregular_graph(n1, n2, d1) with one prior per group (sorted label order, the corrected evidence of
+    strict_reference=False): the oracle's matrices, the exact update count and the half-update iterates
+    [(S1_1, S2_1), (S1_2, S2_2), ...] of oracle.iterate_bipartite with C1 = C2 = 0.5."""
+
+    def __init__(self, n1, n2, d1, symmetric1, symmetric2, lbd, bits=2, mantissa=24, matched=False):
+        from oracle import simrank_oracle as O
+        self.n1, self.n2, self.lbd = n1, n2, lbd
+        self.df = (matched_biregular_graph if matched else biregular_graph)(n1, n2, d1, seed=n1 + n2)
+        base = O.fit_bipartite_pp(self.df, C1=0.5, C2=0.5, iterations=0, verbose=False, strict_reference=False)
+        assert np.array_equal(base["W1"], base["G12"]) and np.array_equal(base["W2"], base["G21"])
+        self.base = base
+        self.A1 = loop_prior(n1, bits, seed=n1 + 10, symmetric=symmetric1)
+        self.A2 = loop_prior(n2, bits, seed=n2 + 20, symmetric=symmetric2)
+        self.exact = exact_updates_bipartite(base["G12"], base["G21"], 0.5, base["E1"], base["E2"], mantissa=mantissa, limit=4,
+                                             prior1=self.A1, prior2=self.A2, lbd1=lbd, lbd2=lbd)
+        print(f"{'matched_' if matched else ''}biregular_graph({n1}, {n2}, {d1}) priors {'sym' if symmetric1 else 'asym'} / {'sym' if symmetric2 else 'asym'}, "
+              f"lbd {lbd}: {self.exact}")
+        self.updates = self.exact.updates
+        self.pairs = []
+        s2 = np.eye(n2)
+        for _ in range(self.updates):
+            s1 = O.update(base["G12"], s2, 0.5, base["E1"], self.A1, lbd)
+            s2 = O.update(base["G21"], s1, 0.5, base["E2"], self.A2, lbd)
+            self.pairs.append((s1, s2))
+
+    def oracle(self, iterations, eps):
+        from oracle import simrank_oracle as O
+        return O.fit_bipartite_pp(self.df, C1=0.5, C2=0.5, iterations=iterations, eps=eps, verbose=False, strict_reference=False,
+                                  apriori1=self.A1, apriori2=self.A2, lbd1=self.lbd, lbd2=self.lbd)
+
+
+_bi_cases = {}
+
+
+def bi_prior_case(n1, n2, d1, lbd, matched, symmetric1, symmetric2):
+    """The BiPriorCase of one entry of BI_PRIOR and one of BI_PRIOR_KINDS, built once and shared."""
+    key = (n1, n2, d1, lbd, matched, symmetric1, symmetric2)
+    if key not in _bi_cases:
+        _bi_cases[key] = BiPriorCase(n1, n2, d1, symmetric1, symmetric2, lbd, matched=matched)
+    return _bi_cases[key]
+
+
+def count_eps(new, old):
+    """The three eps of a stepped count, each with NumPy's count under strict >: [0] an eps below every difference but
+    zero, [1] a difference that occurs in the update — the largest but one where there are two, so that the elements that
+    moved by exactly eps do not count and the ones above do —, [2] that minus one grid step (0.0 where that is all there
+    is): the elements of [1]'s tie count again.  Differences of two iterates on a common grid are representable."""
+    diff = np.abs(new - old)
+    top = float(diff.max())
+    below = diff[(diff < top) & (diff > 0)]
+    tie = float(below.max()) if below.size else top
+    step = 2.0 ** min(lowbit_exp(new), lowbit_exp(old))
+    less = max(tie - step, 0.0)
+    assert float(np.float32(tie)) == tie and float(np.float32(less)) == less
+    return [(eps, int((diff > eps).sum())) for eps in (1e-30, tie, less)]
 
 
 def tie_eps(iterates, fmt=np.float32):

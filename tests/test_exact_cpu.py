@@ -280,3 +280,139 @@ def test_exact_updates_on_the_graph_with_rows_of_16():
     assert k == 1 and np.array_equal(S, its[1])
     S, k = O.iterate_directed(G, 0.5, U, eps - step)
     assert k is None and np.array_equal(S, its[2])
+
+
+# ---- whole loops with a prior (tests/test_gpu_exact_priors.py) ------------------------------------------------------
+# exact updates of (1 - lbd) * E * 0.5 * W S W^T + lbd * A with a 2-bit prior: graph -> {lbd: updates}; the same for a
+# symmetric and an asymmetric prior.  (Loop limit 8; 4 from 2000 nodes on.)
+_PRIOR_U = {("regular", 300, 2): {0.5: 8, 0.25: 4}, ("regular", 1031, 4): {0.5: 3, 0.25: 2}, ("regular", 2100, 2): {0.5: 4, 0.25: 4},
+            ("regular", 2100, 4): {0.5: 3, 0.25: 2}, ("regular", 512, 4): {0.5: 3, 0.25: 2}}
+
+
+def _prior_pins(c, fmt=np.float32):
+    """What the GPU tests lean on, for one PriorCase: iterates unchanged by a cast to the format, asymmetric at more than n
+    places where the prior is (a transposed answer cannot pass), a tie eps with a representable step, and the loop index
+    of the oracle's loop at that eps and one step below."""
+    U = c.updates
+    assert U >= 2
+    its = c.iterates()
+    for u, S in enumerate(its):
+        assert np.array_equal(S.astype(fmt).astype(np.float64), S)
+        assert np.array_equal(np.diag(S), np.ones(c.n))
+        if u >= 1 and not c.symmetric:
+            assert int((S != S.T).sum()) > c.n, u
+        elif u >= 1:
+            assert np.array_equal(S, S.T)
+    Ut, eps, step = X.tie_eps(its, fmt=fmt)
+    assert 2 <= Ut <= U and np.any(np.abs(its[Ut - 1] - its[Ut - 2]) == eps)
+    S, k = c.oracle(Ut, eps)
+    assert k == Ut - 1 and S is its[Ut - 1]
+    S, k = c.oracle(Ut, eps - step)
+    assert k is None and S is its[Ut]
+    return Ut, eps, step
+
+
+@pytest.mark.parametrize("graph", X.PRIOR_GRAPHS + X.PRIOR_RANK_GRAPHS[:1])
+@pytest.mark.parametrize("symmetric", [True, False])
+@pytest.mark.parametrize("lbd", X.PRIOR_LBD)
+def test_exact_updates_with_a_prior(graph, symmetric, lbd):
+    """The table of DESIGN.md §7: exact_updates with the blend booked (and, for an asymmetric prior, both legs on the iterate
+    and its transpose) asserts oracle.update's bits at every counted update itself; here the counts, and the pins."""
+    c = X.prior_case(graph, symmetric, lbd)
+    assert c.updates == _PRIOR_U[graph][lbd] and c.exact().bits <= 24
+    assert np.array_equal(c.A, c.A.T) == symmetric and len(set(np.diag(c.A))) == c.n and not np.any(np.diag(c.A) == 1)
+    Ut, eps, step = _prior_pins(c)
+    if c.n < 2000:                                      # (the oracle's own loop, once more, where it costs little)
+        S, k = O.iterate_directed(c.G, 0.5, Ut, eps, E=c.E, apriori=c.A, lbd=lbd)
+        assert k == Ut - 1 and np.array_equal(S, c.iterates()[Ut - 1])
+        S, k = O.iterate_directed(c.G, 0.5, c.updates, 1e-30, E=c.E, apriori=c.A, lbd=lbd)
+        want = c.oracle(c.updates, 1e-30)               # (k is not None where the loop reaches its fixed point exactly)
+        assert k == want[1] and np.array_equal(S, want[0])
+
+
+def test_exact_updates_refuse_what_the_blend_rounds():
+    """The bookkeeping sees the blend: a prior one bit below the grid the budget allows costs updates, one 20 bits below
+    leaves none; and it refuses an update that is not the oracle's (a transposed prior)."""
+    c = X.prior_case(("regular", 300, 2), False, 0.5)
+    fine = X.exact_updates(c.G, 0.5, c.E, limit=8, prior=c.A + 2.0 ** -22 * (1 - np.eye(c.n)), lbd=0.5).updates
+    assert 1 <= fine < c.updates
+    assert X.exact_updates(c.G, 0.5, c.E, limit=8, prior=c.A + 2.0 ** -30 * (1 - np.eye(c.n)), lbd=0.5).updates == 0
+    r = X._one_update(c.G, c.iterates()[1], 0.5, c.E, 24, c.A, 0.5)
+    assert np.array_equal(r[0], c.iterates()[2])
+    with pytest.raises(AssertionError, match="not the oracle's"):
+        X._is_oracle_update(c.G, c.iterates()[1], 0.5, c.E, c.A.T, 0.5, r[0])
+
+
+@pytest.mark.parametrize("degrees,updates", [((1, 2, 4, 8), 2), ((2, 4), 3)])
+def test_hub_graph_with_a_prior_and_no_evidence(degrees, updates):
+    """pow2_degree_graph(1031, degrees, 48, 0.5): in-degrees from the set, no self loop, no repeated edge, row scales powers of
+    two, half of all references on 48 hub columns that 40 rows and more (32 and more for degrees 2 and 4) reference; exact
+    updates of the plan-level loop with a prior and WITHOUT the evidence factor."""
+    graph = ("hubs", 1031, degrees)
+    df = X.loop_graph(graph)
+    assert set(df.groupby("to").size()) == set(degrees) and not (df["from"] == df["to"]).any()
+    refs = np.bincount(df["from"], minlength=1031)
+    assert refs[:48].sum() == len(df) // 2 and refs[:48].min() >= (40 if 8 in degrees else 32) and refs[48:].max() < 20
+    for symmetric in (True, False):
+        c = X.prior_case(graph, symmetric, 0.5, evidence=False)
+        assert X.is_pow2_or_zero(c.G.max(axis=1)) and c.E is None
+        assert c.updates == updates
+        _prior_pins(c)
+
+
+@pytest.mark.parametrize("n1,n2,d1,lbd,matched", X.BI_PRIOR)
+@pytest.mark.parametrize("sym1,sym2", X.BI_PRIOR_KINDS)
+def test_exact_updates_of_the_two_matrix_loop_with_priors(n1, n2, d1, lbd, matched, sym1, sym2):
+    c = X.bi_prior_case(n1, n2, d1, lbd, matched, sym1, sym2)
+    assert c.updates >= 2
+    want = c.oracle(c.updates, 1e-30)
+    last = c.pairs[-1] if want["k"] is None else c.pairs[want["k"] - 1]      # (d1 = 1 reaches its fixed point exactly)
+    assert np.array_equal(want["S1"], last[0]) and np.array_equal(want["S2"], last[1])
+    for s1, s2 in c.pairs:
+        for S in (s1, s2):
+            assert np.array_equal(S.astype(np.float32).astype(np.float64), S)
+        a1, a2 = int((s1 != s1.T).sum()), int((s2 != s2.T).sum())
+        if sym1 and sym2:
+            assert a1 == a2 == 0
+        else:
+            assert (a2 if sym1 else a1) > (n2 if sym1 else n1)           # the side of the asymmetric prior
+    if matched and not (sym1 and sym2):
+        s1, s2 = c.pairs[-1]                                              # ... and there it reaches the other side too
+        assert int((s1 != s1.T).sum()) > n1 and int((s2 != s2.T).sum()) > n2
+
+
+def test_exact_updates_with_a_prior_in_the_other_formats():
+    """float64: the theoretical grid; fp16-held matrices: 11 bits and a 1-bit prior, two updates on the graphs with d = 2,
+    one only with d = 4 and on the bipartite pairs, which are left out on the GPU for that."""
+    for graph in X.PRIOR_F64:
+        for symmetric in (True, False):
+            c = X.prior_case(graph, symmetric, 0.5, mantissa=53)
+            assert c.updates > X.prior_case(graph, symmetric, 0.5).updates or c.updates == 10
+            assert X.tie_eps(c.iterates(), fmt=np.float64)[0] >= 2
+    for graph in X.PRIOR_FP16:
+        c = X.prior_case(graph, True, 0.5, bits=1, mantissa=11)
+        assert c.updates == 2 and float(np.abs(c.A).max()) < 3.99
+        for S in c.iterates():
+            assert np.array_equal((S * 16384.0).astype(np.float16).astype(np.float64), S * 16384.0)
+        assert np.array_equal((c.A * 16384.0).astype(np.float16).astype(np.float64), c.A * 16384.0)
+    assert X.prior_case(("regular", 512, 4), True, 0.5, bits=1, mantissa=11).updates == 1
+    assert X.BiPriorCase(256, 256, 2, True, True, 0.5, bits=1, mantissa=11).updates == 1
+
+
+def test_lowbit_exp_reads_the_bits_as_frexp_and_log2_did():
+    """lowbit_exp takes mantissa and exponent from the float64 word; the earlier form went through frexp and log2.  The same
+    answer on integers times a power of two, on 1 - 2^-k, on a scalar, on zeros and on values 2^-40 apart."""
+    def earlier(a):
+        a = np.asarray(a, dtype=np.float64)
+        a = a[a != 0]
+        if a.size == 0:
+            return None
+        m, e = np.frexp(np.abs(a))
+        mant = (m * 2.0 ** 53).astype(np.int64)
+        low = mant & -mant
+        return int((e.astype(np.int64) - 53 + np.log2(low.astype(np.float64)).astype(np.int64)).min())
+    rng = np.random.default_rng(0)
+    for a in (rng.integers(-2 ** 20, 2 ** 20, (200, 200)) * 2.0 ** -17, np.array([0.75, -3.0, 0.0, 2.0 ** -40]), np.array([[1.0]]),
+              rng.random((100, 100)), np.float64(0.5), 1 - 0.5 ** rng.integers(0, 60, (50, 50)).astype(float), np.zeros(4),
+              rng.integers(1, 2 ** 52, 1000).astype(np.float64) * 2.0 ** -300):
+        assert X.lowbit_exp(a) == earlier(a)
