@@ -502,6 +502,9 @@ SIMRANK_API int simrank_plan_info(const simrank_plan* p, int64_t* n, int32_t* up
  * What leg 2 of the LATEST update took (tuning "leg2_short"):
  *      "leg2_short_groups"  groups of four 32-row tiles whose workgroups ran the short path of the upper-triangle gather
  *                        leg 2 (0: the knob is off, no group is short, or the launch was another kernel or instantiation)
+ * The plan's (per group: that group's) pattern object, read-only, owned by the plan and valid until simrank_*_destroy:
+ *      "graph"           address of the simrank_graph (simrank_plan and simrank_biplan only; what simrank_plan_info hands
+ *                        out), for simrank_graph_get / simrank_graph_fused_stats / simrank_graph_dense_stats
  * simrank_biplan_get answers the same keys per group (layout 0).  simrank_shardplan_get answers them for the rank's
  * column block: layout 1 (f32 row-major, "iterate_stride" = ld) or 2 (fp16-held, "iterate_stride" = rows_pad), n rows,
  * columns [col_lo, col_hi) of the solver's order; the block's column ids are "ids" + col_lo (the same values as

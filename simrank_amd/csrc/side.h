@@ -325,6 +325,7 @@ inline int side_get(const side_t& a, const char* key, int64_t* value) {
     else if (!strcmp(key, "leg1_units")) *value = a.leg1_units;
     else if (!strcmp(key, "leg1_skipped")) *value = a.leg1_skipped;
     else if (!strcmp(key, "leg2_short_groups")) *value = a.leg2_short_groups;
+    else if (!strcmp(key, "graph")) *value = (int64_t)(uintptr_t)a.g;
     else SR_REQUIRE(false, "unknown plan key '%s'", key);
     return SIMRANK_OK;
 }

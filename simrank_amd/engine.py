@@ -554,6 +554,10 @@ class BiPlan(_Owner):
     def get(self, group: int, key: str) -> int:
         return self.side(group - 1).get(key)
 
+    def graph_handle(self, group: int):
+        """Group 1 | 2's graph object (for simrank_graph_get / _fused_stats / _dense_stats); owned by the plan."""
+        return C.c_void_p(self.get(group, "graph"))
+
     def evidence_counts(self, group: int) -> np.ndarray:
         return self.side(group - 1).evidence_counts()
 

@@ -110,27 +110,28 @@ Symmetric = namedtuple("Symmetric", "S Tt KS KT used1 used2")
 
 
 def summable_symmetric(csr, mantissa=24, headroom=0, seed=0, exponent=0):
-    """A symmetric integer S = diag(d) + N (x 2^exponent) for a SQUARE pattern such that both legs of W . S . W^T are exactly
-    summable: leg 1's operand is S, leg 2's is Tt = (W . S)^T, and the product is exactly symmetric — what the upper-triangle
-    forms mirror.  d is wide (one odd value of m-h-3 .. m-h-2 bits per column after leg 1, as summable_operand has them), N is
-    a symmetric matrix of small integers of both signs, so no element of Tt is zero for lack of a term.
+    """A symmetric integer S = diag(d) + N (x 2^exponent), K x K for an n x K pattern (K = n: a square one), such that both
+    legs of W . S . W^T are exactly summable: leg 1's operand is S, leg 2's is Tt = (W . S)^T — K x n — and the product (n x n)
+    is exactly symmetric — what the upper-triangle forms mirror.  d is wide (one odd value of m-h-3 .. m-h-2 bits per column
+    after leg 1, as summable_operand has them), N is a symmetric matrix of small integers of both signs, so no element of Tt
+    is zero for lack of a term.
     -> (S, Tt, integer S, integer (pattern . S), budget share of leg 1, of leg 2)."""
-    assert csr.n_rows == csr.n_cols and is_pow2_or_zero(csr.rowscale)
-    n, bits = csr.n_rows, mantissa - headroom
+    assert is_pow2_or_zero(csr.rowscale)
+    K, bits = csr.n_cols, mantissa - headroom
     rng = np.random.default_rng(seed)
     longest = longest_row(csr)
     # leg 2 sums |(P S)[a, j]| over j in row b: <= longest * (|d| + longest * nmax)  -> d gets what a row allows, N the rest
     wd = _entry_bits(bits, longest) - 1
     nbits = max(1, min(4, bits - 2 - 2 * int(np.ceil(np.log2(max(1, longest))))))
-    d = rng.integers(2 ** (wd - 1), 2 ** wd, size=n, dtype=np.int64) | 1
-    d *= rng.choice(np.array([-1, 1], dtype=np.int64), size=n)
-    N = rng.integers(-(2 ** nbits) + 1, 2 ** nbits, size=(n, n), dtype=np.int64)
+    d = rng.integers(2 ** (wd - 1), 2 ** wd, size=K, dtype=np.int64) | 1
+    d *= rng.choice(np.array([-1, 1], dtype=np.int64), size=K)
+    N = rng.integers(-(2 ** nbits) + 1, 2 ** nbits, size=(K, K), dtype=np.int64)
     N = np.triu(N, 1)
     N = N + N.T
     P = pattern(csr)
     # one diagonal entry in 16 as wide as the budget takes (where it reaches 17 bits, the hi, mid and lo terms of its split
     # are all non-zero); rows that hold several of them decide how wide that is
-    big = np.arange(n) % 16 == 5
+    big = np.arange(K) % 16 == 5
     mag = rng.random(int(big.sum()))
     for wb in range(bits - 2, wd, -1):
         dd = d.copy()
@@ -149,6 +150,7 @@ def summable_symmetric(csr, mantissa=24, headroom=0, seed=0, exponent=0):
     S = np.ldexp(KS.astype(np.float64), exponent)
     rs = np.asarray(csr.rowscale, dtype=np.float64)
     Tt = (rs[:, None] * np.ldexp(KT.astype(np.float64), exponent)).T.copy()
+    assert S.shape == (K, K) and Tt.shape == (K, csr.n_rows)
     return Symmetric(S, Tt, KS, KT, used1, worst2 / 2.0 ** bits)
 
 
@@ -376,6 +378,69 @@ def pow2_degree_graph(n, degrees, hubs, share, seed):
     assert not df.duplicated(["from", "to"]).any() and not (df["from"] == df["to"]).any()
     assert set(df.groupby("to").size()) <= set(degrees) and df["to"].nunique() == n
     return df
+
+
+def stable_length_order(lengths):
+    """planprep.hip length_order restated: the nodes in ascending row length, equal lengths in the caller's order."""
+    return np.argsort(np.asarray(lengths), kind="stable").astype(np.int32)
+
+
+def pow2_bidegree_graph(deg1, deg2, seed):
+    """Bipartite edge list (user, item, weight = 1) with PRESCRIBED degree sequences on both sides (powers of two, equal
+    totals; both are shuffled here): a random matching of the stubs, repeated pairs repaired by swapping items between two
+    edges.  Every node is present, users are 0 .. n1 - 1 and items 0 .. n2 - 1 (so the sorted label order is the index).
+    Asserted: the degree sets, no repeated pair, that the stable length order of EACH side is a real permutation, and — for
+    n1 = n2 — that the two orders differ."""
+    rng = np.random.default_rng(seed)
+    deg1, deg2 = np.array(deg1, dtype=np.int64), np.array(deg2, dtype=np.int64)
+    assert deg1.sum() == deg2.sum() and all(d > 0 and d & (d - 1) == 0 for d in set(deg1.tolist()) | set(deg2.tolist()))
+    rng.shuffle(deg1)
+    rng.shuffle(deg2)
+    users = np.repeat(np.arange(deg1.size, dtype=np.int64), deg1)
+    items = rng.permutation(np.repeat(np.arange(deg2.size, dtype=np.int64), deg2))
+    E = users.size
+    for _ in range(200):
+        key = users * deg2.size + items
+        order = np.argsort(key, kind="stable")
+        dup = order[1:][key[order][1:] == key[order][:-1]]
+        if dup.size == 0:
+            break
+        have = set(key.tolist())
+        for i in dup.tolist():
+            for j in rng.integers(0, E, size=64).tolist():
+                a, b = users[i] * deg2.size + items[j], users[j] * deg2.size + items[i]
+                if a not in have and b not in have and users[i] != users[j]:
+                    items[i], items[j] = items[j], items[i]
+                    have.update((int(a), int(b)))
+                    break
+    else:
+        raise AssertionError("repeated pairs could not be repaired")
+    df = pd.DataFrame({"user": users, "item": items, "weight": 1.0})
+    assert not df.duplicated(["user", "item"]).any()
+    got1, got2 = np.bincount(users, minlength=deg1.size), np.bincount(items, minlength=deg2.size)
+    assert np.array_equal(got1, deg1) and np.array_equal(got2, deg2)
+    o1, o2 = stable_length_order(deg1), stable_length_order(deg2)
+    for o in (o1, o2):
+        assert not np.array_equal(o, np.arange(o.size)), "the length order is the identity"
+    assert deg1.size != deg2.size or not np.array_equal(o1, o2)
+    return df
+
+
+# the graphs of tests/test_gpu_exact_bipartite.py: name -> (degrees of the users, of the items, seed).  Both sides hold
+# mixed power-of-two degrees, so both length orders are real permutations; node counts are multiples of 128, so that a
+# sharded plan deals its order on 2 and 4 ranks.  "hub": 48 items that 8 users each reference — dense sets for the matrix
+# cores in the USERS' pattern (the hub COLUMNS are group 1's).
+BI_MIXED = {"mixed384": ([1] * 256 + [2] * 128, [1] * 256 + [2] * 128, 384),
+            "mixed512": ([1] * 256 + [2] * 256, [2] * 128 + [4] * 128, 512),
+            "hub512": ([1] * 256 + [2] * 256, [8] * 48 + [1] * 128 + [2] * 128, 560)}
+_bi_graphs = {}
+
+
+def bi_graph(name):
+    """pow2_bidegree_graph of BI_MIXED[name], once."""
+    if name not in _bi_graphs:
+        _bi_graphs[name] = pow2_bidegree_graph(*BI_MIXED[name])
+    return _bi_graphs[name]
 
 
 def loop_prior(n, bits, seed, symmetric, density=1.0, half=False):
@@ -666,6 +731,105 @@ def bi_prior_case(n1, n2, d1, lbd, matched, symmetric1, symmetric2):
     return _bi_cases[key]
 
 
+class BiLoop:
+    """One two-matrix loop on bi_graph(name), C1 = C2 = 0.5: `pp` (the evidence factors; E2 = E1 position by position when
+    `strict`), priors (`kinds` = (symmetric1, symmetric2) of 2-bit loop_priors, or None) with `lbd`.  The oracle's matrices,
+    the exact update count (exact_updates_bipartite on the oracle's G12, G21, E1, E2) and the half-update iterates
+    [(S1_1, S2_1), ...] of oracle.iterate_bipartite.  Built once per argument list (bi_loop); nobody writes to it."""
+
+    def __init__(self, name, pp=False, strict=False, kinds=None, lbd=0.5, mantissa=24):
+        from oracle import simrank_oracle as O
+        self.O = O                                       # (imported here, as everywhere in this module: once per loop)
+        self.name, self.pp, self.strict, self.kinds, self.lbd, self.mantissa = name, pp, strict, kinds, lbd, mantissa
+        self.df = bi_graph(name)
+        base = O.fit_bipartite_pp(self.df, C1=0.5, C2=0.5, iterations=0, verbose=False, strict_reference=False)
+        assert np.array_equal(base["W1"], base["G12"]) and np.array_equal(base["W2"], base["G21"])
+        self.G12, self.G21 = base["G12"], base["G21"]
+        self.n1, self.n2 = self.G12.shape
+        self.lab1, self.lab2 = list(base["sorted1"]), list(base["sorted2"])
+        assert self.lab1 == list(range(self.n1)) and self.lab2 == list(range(self.n2))
+        assert not strict or (pp and self.n1 == self.n2)
+        self.E1 = base["E1"] if pp else None
+        self.E2 = (base["E1"] if strict else base["E2"]) if pp else None
+        self.A1 = self.A2 = None
+        if kinds is not None:
+            self.A1 = loop_prior(self.n1, 2, seed=self.n1 + 10, symmetric=kinds[0])
+            self.A2 = loop_prior(self.n2, 2, seed=self.n2 + 20, symmetric=kinds[1])
+        self.exact = exact_updates_bipartite(self.G12, self.G21, 0.5, self.E1, self.E2, mantissa=mantissa,
+                                             limit=4 if mantissa < 53 else 6, prior1=self.A1, prior2=self.A2,
+                                             lbd1=lbd if kinds else None, lbd2=lbd if kinds else None)
+        print(f"bi_graph({name!r}) {'++' if pp else 'plain'}{' strict' if strict else ''} priors {kinds} lbd {lbd} "
+              f"mantissa {mantissa}: {self.exact}")
+        self.updates = self.exact.updates
+        self.pairs = []
+        s2 = np.eye(self.n2)
+        for _ in range(self.updates):
+            s1 = self.update(1, s2)
+            s2 = self.update(2, s1)
+            self.pairs.append((s1, s2))
+
+    def update(self, group, S_other):
+        O = self.O
+        W, E, A = (self.G12, self.E1, self.A1) if group == 1 else (self.G21, self.E2, self.A2)
+        if A is not None:
+            return O.update(W, S_other, 0.5, 1.0 if E is None else E, A, self.lbd)
+        return O.update(W, S_other, 0.5, E)
+
+    def oracle(self, iterations, eps):
+        """(S1, S2, k) of oracle.iterate_bipartite, from the cached half-updates."""
+        O = self.O
+        assert iterations <= self.updates
+        old, new = (np.zeros((self.n1, self.n1)), np.zeros((self.n2, self.n2))), (np.eye(self.n1), np.eye(self.n2))
+        for k in range(iterations):
+            if O.converged(old[0], new[0], eps) and O.converged(old[1], new[1], eps):
+                return new[0], new[1], k
+            old, new = new, self.pairs[k]
+        return new[0], new[1], None
+
+    def lengths(self, group):
+        """Row lengths of the group's pattern in the caller's order."""
+        return ((self.G12 if group == 1 else self.G21) != 0).sum(axis=1)
+
+    def tie_eps(self):
+        """-> (U, eps, step): eps = the largest difference of either group between the states the loop compares at index
+        U - 1 (the half-updates U - 1 and U - 2; state 0 is the identity pair) — the test there passes only under strict > —
+        and the grid step of those states; asserted: the oracle's loop stops at U - 1 with eps and runs on with eps - step."""
+        fmt = np.float64 if self.mantissa == 53 else np.float32
+        U = self.updates
+        states = [(np.eye(self.n1), np.eye(self.n2))] + self.pairs
+        while U > 2 and all(np.array_equal(states[U - 1][j], states[U - 2][j]) for j in (0, 1)):
+            U -= 1
+        assert U >= 2
+        new, old = states[U - 1], states[U - 2]
+        eps = max(float(np.abs(new[j] - old[j]).max()) for j in (0, 1))
+        step = 2.0 ** min(lowbit_exp(m) for m in new + old)
+        assert eps >= step > 0 and float(fmt(eps)) == eps and float(fmt(eps - step)) == eps - step
+        assert self.oracle(U, eps)[2] == U - 1 and self.oracle(U, eps - step)[2] is None
+        return U, eps, step
+
+
+def dealt_order(order, deal):
+    """planprep.hip deal_order restated: the ascending order dealt to `deal` shards in runs of 128 (32) nodes, where the node
+    count divides evenly; else the order itself."""
+    order = np.asarray(order)
+    n = order.size
+    if deal <= 1 or n % (32 * deal):
+        return order
+    unit = 128 if n % (128 * deal) == 0 else 32
+    per = n // (unit * deal)
+    return order.reshape(per, deal, unit).transpose(1, 0, 2).reshape(n)
+
+
+_bi_loops = {}
+
+
+def bi_loop(name, pp=False, strict=False, kinds=None, lbd=0.5, mantissa=24):
+    key = (name, pp, strict, kinds, lbd, mantissa)
+    if key not in _bi_loops:
+        _bi_loops[key] = BiLoop(*key)
+    return _bi_loops[key]
+
+
 def count_eps(new, old):
     """The three eps of a stepped count, each with NumPy's count under strict >: [0] an eps below every difference but
     zero, [1] a difference that occurs in the update — the largest but one where there are two, so that the elements that
@@ -755,7 +919,8 @@ def leg2_case(n, variant, mantissa=24, seed=None, exponent=0):
 
 
 def leg2_on(csr, variant, mantissa=24, seed=0, exponent=0):
-    """leg2_case on a given square pattern (row scales powers of two)."""
+    """leg2_case on a given pattern, n x K (row scales powers of two): the operand Tt is K x n, the counts, the prior and the
+    result n x n."""
     n = csr.n_rows
     h = HEADROOM[variant] if mantissa == 24 else 0
     sym = summable_symmetric(csr, mantissa=mantissa, headroom=h, seed=seed, exponent=exponent)
@@ -769,6 +934,18 @@ def leg2_on(csr, variant, mantissa=24, seed=0, exponent=0):
     want = exact_epilogue(product64(csr, sym.Tt), 0.5, counts, prior, lbd)
     assert np.array_equal(want, want.T)
     return csr, sym, counts, prior, lbd, want
+
+
+# leg 2 on RECTANGULAR patterns (tests/test_gpu_exact_rect.py): (rows n, operand rows K) — K < n and K > n, the operand's
+# rows_pad above and below the result's, and K = 20: fewer operand rows than a panel has columns
+LEG2_RECT = [(129, 77), (520, 333), (64, 1000), (1031, 2100), (2100, 700), (660, 20)]
+LEG2_RECT_BELOW = (63, 200)                             # fewer than 64 rows: no upper-triangle form
+
+
+def rect_case(M, K, variant, mantissa=24, exponent=0):
+    """leg2_case on corner_case(M, K, M + K, hubs=min(K, 150)): a symmetric leg 2 whose pattern is M x K."""
+    seed = M + K
+    return leg2_on(corner_case(M, K, seed, hubs=min(K, 150)), variant, mantissa, seed, exponent)
 
 
 # ---- graphs built for leg 2's short path (tests/test_gpu_exact_short.py; the rule: tests/leg2_rule.py) -------------------
@@ -810,15 +987,16 @@ SHORT_EQUAL = ("equal8", "equal16")
 _short = {}
 
 
-def short_case(name, variant):
+def short_case(name, variant, K=None):
     """leg2_case on short_lengths()[name]: -> (csr, Symmetric, counts, prior, lbd, want float64, row lengths).  Built once
-    per (name, variant) and shared: nobody writes to what this returns."""
-    key = (name, variant)
+    per (name, variant, K) and shared: nobody writes to what this returns.  `K`: the pattern's columns (None: as many as
+    rows) — the same row lengths on a rectangular pattern."""
+    key = (name, variant) if K is None else (name, variant, K)
     if key not in _short:
         from tests import leg2_rule as R
         lengths, seed = short_lengths()[name]
-        csr = pow2_rowscale(R.from_lengths(lengths, seed), seed)
-        assert np.array_equal(np.diff(csr.rowptr), lengths)
+        csr = pow2_rowscale(R.from_lengths(lengths, seed, K), seed)
+        assert np.array_equal(np.diff(csr.rowptr), lengths) and csr.n_cols == (len(lengths) if K is None else K)
         _short[key] = leg2_on(csr, variant, seed=seed) + (list(lengths),)
     return _short[key]
 
@@ -840,11 +1018,11 @@ def tie_places_every_row(n, panel=32):
 _planted = {}
 
 
-def short_planted(name, variant):
+def short_planted(name, variant, K=None):
     """-> (want float32, Planted with all three kinds, Planted with "on" and "below" only) at tie_places_every_row; once."""
-    key = (name, variant)
+    key = (name, variant) if K is None else (name, variant, K)
     if key not in _planted:
-        want = short_case(name, variant)[5]
+        want = short_case(name, variant, K)[5]
         want32 = want.astype(np.float32)
         assert np.array_equal(want32.astype(np.float64), want)
         places = tie_places_every_row(want.shape[0])

@@ -6,17 +6,19 @@ import numpy as np
 from simrank_amd.ingest import CSR
 
 
-def from_lengths(lengths, seed):
+def from_lengths(lengths, seed, K=None):
     """Rows of exactly these lengths, columns drawn without repetition; the caller's order (a plan keeps it with
-    reorder = False, a graph made by HipOps.graph always)."""
+    reorder = False, a graph made by HipOps.graph always).  `K`: the number of columns (None: as many as rows)."""
     n = len(lengths)
+    K = n if K is None else K
+    assert max(lengths, default=0) <= K
     rng = np.random.default_rng(seed)
-    rows = [np.sort(rng.choice(n, size=k, replace=False)).astype(np.int32) for k in lengths]
+    rows = [np.sort(rng.choice(K, size=k, replace=False)).astype(np.int32) for k in lengths]
     rowptr = np.zeros(n + 1, dtype=np.int32)
     rowptr[1:] = np.cumsum(lengths)
     col = np.concatenate(rows + [np.zeros(0, dtype=np.int32)]).astype(np.int32)
     deg = np.asarray(lengths, dtype=np.float64)
-    return CSR(n, n, rowptr, col, np.where(deg > 0, 1.0 / np.maximum(deg, 1), 0.0))
+    return CSR(n, K, rowptr, col, np.where(deg > 0, 1.0 / np.maximum(deg, 1), 0.0))
 
 
 def boundary_lengths(ragged=20):

@@ -382,6 +382,38 @@ def _check_counts(run, want32, what, planted=None):
     assert exact == 0 and some == 0, (what, exact, some)           # ties and near misses: a >= would count them
 
 
+# every form of leg 2 with the epilogue: (what, knobs of the graph, panel-blocked operands, upper triangle + mirror) — shared
+# with tests/test_gpu_exact_rect.py, which runs the same list on rectangular patterns
+LEG2_FORMS = [("row-major full (gather3)", dict(fuse=0), False, False),
+              ("row-major triangle (gather3)", dict(fuse=0), False, True),
+              ("row-major full, panel 64 (emit_row)", dict(fuse=0, panel=64), False, False),
+              ("row-major triangle, lean=0 (emit_row)", dict(fuse=0, lean=0), False, True),
+              ("row-major, block-dense part", dict(fuse=0, dense_min=3, dense_cols=32, dense_sym=1), False, True),
+              ("blocked one-launch (fused)", dict(fuse_sym=1), True, True),
+              ("blocked one-launch, 32-bit ids", dict(fuse_sym=1, ids16=0), True, True),
+              ("blocked one-launch, split blocks", dict(fuse_sym=1, fuse_min=3, fuse_steps=2, fuse_unit=4, fuse_rows=400), True, True),
+              ("blocked one-launch, fuse_group 1", dict(fuse_sym=1, fuse_group=1), True, True),
+              ("blocked two-launch (gather3 kSym)", dict(fuse_sym=0), True, True),
+              # ... and the same leg saying which of its two paths it runs (dense_sym=0: no dense part whatever the
+              # pattern, so that the launch is the one the rule of tests/leg2_rule.py speaks about)
+              ("blocked two-launch, general path (gather3 kSym)", dict(fuse_sym=0, dense_sym=0, balance=2, leg2_short=0), True, True),
+              ("blocked two-launch, short path (gather3 kSym SHORT)", dict(fuse_sym=0, dense_sym=0, balance=2, leg2_short=16), True, True),
+              ("blocked full form", dict(fuse_sym=0), True, False)]
+
+
+def _leg2_scalar(ops, g, tt32, n, counts, prior, lbd, prev):
+    """An ld off the 16-byte grid: the scalar kernel (no triangle form there).  -> as _leg2."""
+    put = lambda a, dtype=np.float32: guarded(ops, a.shape[0], a.shape[1], a, dtype, pad=1)
+    x, y = put(tt32), guarded(ops, n, n, pad=1)
+    ep = _ep(put, counts, prior, lbd, prev, False)
+    ops.spmm(g, x, y, epilogue=ep)
+    got, exact = ops.download(y), ops.read_changed()
+    ops.spmm(g, x, y, epilogue=dict(ep, count_any=True))
+    some = ops.read_changed()
+    check_untouched(ops, x, y)
+    return got, exact, some
+
+
 @pytest.mark.parametrize("n", X.LEG2_N)
 @pytest.mark.parametrize("variant", ["plain", "evidence", "all"])
 def test_leg2_every_form_gives_the_reference_bits_and_the_strict_count(ops, n, variant):
@@ -391,23 +423,8 @@ def test_leg2_every_form_gives_the_reference_bits_and_the_strict_count(ops, n, v
     leg with the block-dense part, and the standalone epilogue (:1468)."""
     csr, sym, counts, prior, lbd, want = X.leg2_case(n, variant)
     want32, tt32 = f32(want), f32(sym.Tt)
-    forms = [("row-major full (gather3)", dict(fuse=0), False, False),
-             ("row-major triangle (gather3)", dict(fuse=0), False, True),
-             ("row-major full, panel 64 (emit_row)", dict(fuse=0, panel=64), False, False),
-             ("row-major triangle, lean=0 (emit_row)", dict(fuse=0, lean=0), False, True),
-             ("row-major, block-dense part", dict(fuse=0, dense_min=3, dense_cols=32, dense_sym=1), False, True),
-             ("blocked one-launch (fused)", dict(fuse_sym=1), True, True),
-             ("blocked one-launch, 32-bit ids", dict(fuse_sym=1, ids16=0), True, True),
-             ("blocked one-launch, split blocks", dict(fuse_sym=1, fuse_min=3, fuse_steps=2, fuse_unit=4, fuse_rows=400), True, True),
-             ("blocked one-launch, fuse_group 1", dict(fuse_sym=1, fuse_group=1), True, True),
-             ("blocked two-launch (gather3 kSym)", dict(fuse_sym=0), True, True),
-             # ... and the same leg saying which of its two paths it runs (dense_sym=0: no dense part whatever the
-             # pattern, so that the launch is the one the rule of tests/leg2_rule.py speaks about)
-             ("blocked two-launch, general path (gather3 kSym)", dict(fuse_sym=0, dense_sym=0, balance=2, leg2_short=0), True, True),
-             ("blocked two-launch, short path (gather3 kSym SHORT)", dict(fuse_sym=0, dense_sym=0, balance=2, leg2_short=16), True, True),
-             ("blocked full form", dict(fuse_sym=0), True, False)]
     lengths = np.diff(csr.rowptr).tolist()
-    for what, kw, blocked, symmetric in forms:
+    for what, kw, blocked, symmetric in LEG2_FORMS:
         with knobs(ops, **kw):
             g = ops.graph(csr)
             if "one-launch" in what:
@@ -420,18 +437,7 @@ def test_leg2_every_form_gives_the_reference_bits_and_the_strict_count(ops, n, v
     # an ld off the 16-byte grid: the scalar kernel (no triangle form there)
     with knobs(ops, fuse=0):
         g = ops.graph(csr)
-
-        def scalar(prev):
-            put = lambda a, dtype=np.float32: guarded(ops, a.shape[0], a.shape[1], a, dtype, pad=1)
-            x, y = put(tt32), guarded(ops, n, n, pad=1)
-            ep = _ep(put, counts, prior, lbd, prev, False)
-            ops.spmm(g, x, y, epilogue=ep)
-            got, exact = ops.download(y), ops.read_changed()
-            ops.spmm(g, x, y, epilogue=dict(ep, count_any=True))
-            some = ops.read_changed()
-            check_untouched(ops, x, y)
-            return got, exact, some
-        _check_counts(scalar, want32, "scalar variant")
+        _check_counts(lambda prev: _leg2_scalar(ops, g, tt32, n, counts, prior, lbd, prev), want32, "scalar variant")
     # the un-fused epilogue on the exact product
 
     def standalone(prev):
@@ -624,9 +630,15 @@ def test_half_leg2_rounds_the_exact_result_once_and_counts_by_its_rule(hops, n, 
     count follows half.hip's header — |new before rounding - old stored| > eps + half the spacing at old — computed from the
     reference, with planted differences a spacing and more off that bound on either side and one exactly on it (the
     diagonal: new = 1, old = 1 - eps - 2^-12 in stored units)."""
-    ops = hops
     e = -6 - int(np.log2(scale))
-    csr, sym, counts, prior, lbd, want = X.leg2_case(n, variant, mantissa=11, exponent=e)
+    half_leg2_protocol(hops, X.leg2_case(n, variant, mantissa=11, exponent=e), scale)
+
+
+def half_leg2_protocol(ops, case, scale):
+    """The protocol of the test above on one case of X.leg2_on (a square pattern, or — tests/test_gpu_exact_rect.py — an
+    n x K one: the operand has K rows, everything else n)."""
+    csr, sym, counts, prior, lbd, want = case
+    n = csr.n_rows
     assert scale == 1.0 or np.abs(want).max() < 4
     want_st = want * scale                                                     # exact, before rounding
     places = [rc for rc in X.tie_places(n, n) if rc[0] < rc[1]]

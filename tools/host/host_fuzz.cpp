@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "common.h"
+#include "side.h"
 
 #define CHECK(c, ...)                                         \
     do {                                                      \
@@ -491,6 +492,13 @@ int main(int argc, char** argv) {
             // ... and the hub columns of the evidence counts: the number chosen, of which the image's width is the next multiple of 32
             CHECK(simrank_graph_get(g, "ev_hubs", &v) == SIMRANK_OK && v == int64_t(g->ev_hub_cols) && (v == 0 || (v >= 8 && v <= 4096)) &&
                       int64_t(g->ev_hubs) == (v + 31) / 32 * 32, "graph_get ev_hubs = %lld", (long long)v);
+            // ... and a plan side's key "graph" (side.h side_get, behind simrank_plan_get and simrank_biplan_get): the handle made here
+            {
+                simrank::side_t side;
+                side.g = g;
+                CHECK(simrank::side_get(side, "graph", &v) == SIMRANK_OK && v == (int64_t)(uintptr_t)g, "side_get graph = %llx",
+                      (unsigned long long)v);
+            }
             v = -7;
             CHECK(simrank_graph_get(g, "no_such_key", &v) == SIMRANK_ERR_INVALID && v == -7 &&
                       strstr(simrank_last_error(), "no_such_key"), "graph_get: unknown key accepted");
