@@ -6,6 +6,8 @@ decide there, once, whether the model is pruned (``lists``) or held in several c
 """
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 import pandas as pd
 
@@ -662,6 +664,102 @@ class _KeptModel:
         return labels, clusters, pd.DataFrame({"moved": np.array(moved, dtype=np.int64),
                                                "changed": np.array(changed, dtype=np.int64),
                                                "objective": np.array(objective, dtype=np.float64)})
+
+    def compare(self, other, tolerances=(1e-5,), top_k=10, floor=0.0):
+        """How far apart two models of one graph are: ``other`` is another estimator holding a model (kept, compact or
+        loaded; any mix of f32, fp16-held and float64; ``other is self`` is allowed and gives all zeros).  Both models
+        must have the same number of groups, the same labels in the same order per group and live on the same device; a
+        pruned model on either side stands for a different matrix P (compare before ``prune``).  Every violation is a
+        ValueError before any device work that names the first difference; a released model is the usual RuntimeError.
+
+        For the elements ``a = S[r, c]`` of this model and ``b`` of ``other``, each widened as ``rows`` widens it: ``d`` is
+        +0.0 if ``a == b`` (so -0.0 and +0.0 agree, and equal infinities agree) or both are NaN, +inf if exactly one is
+        NaN, otherwise ``fabs(a - b)``; ``rel`` is +0.0 if ``d == 0`` or ``max(|a|, |b|) < floor``, +inf if ``d == inf``,
+        otherwise ``d / max(|a|, |b|)``, the first rule that applies (a NaN operand is below no floor).  The diagonal is included.  ``tolerances``: 0 to 7 finite numbers >= 0;
+        ``floor``: a finite number >= 0; ``top_k``: None or a positive int, clamped to N - 1 (above 4096 after that: a
+        ValueError).
+
+        -> ``(summary, nodes, histogram)``; a tuple of two such triples for the bipartite classes.
+
+        ``nodes``, indexed by the dense frame's labels in its order: ``max_abs`` (float64) the largest ``d`` of the
+        node's row and ``at`` the label of the first column attaining it, ``max_rel`` and ``at_rel`` the same for
+        ``rel``, ``differing`` (int64) the columns with ``d > 0`` and one ``over@<tol>`` column (int64) per tolerance: the
+        columns with ``d > tol``.  With ``top_k=k`` also ``overlap``: how many nodes both models' k best OTHER nodes of
+        the row share, and ``same_prefix``: the number of leading ranks at which both lists name the same node; the
+        lists are ``most_similar``'s, in the project's total order, so they are functions of the matrices alone.
+
+        ``summary``, one row: ``entries`` (N^2), ``differing``, ``max_abs`` with its pair ``node`` and ``neighbor``,
+        ``max_rel`` with ``node_rel`` and ``neighbor_rel`` (a maximum attained more than once: the first pair in
+        row-major order), the ``over@<tol>`` totals (int64) and, with ``top_k``, ``mean_overlap`` and
+        ``identical_lists``: the nodes with ``same_prefix == k``.
+
+        ``histogram``: an int64 Series over the 2048 exponent bins ``bits(d) >> 52``, indexed by the bin number: bin 0
+        holds ``d == 0`` and subnormal ``d``, bin e holds ``2^(e-1023) <= d < 2^(e-1022)``, bin 2047 holds ``d == inf``.
+
+        Nothing is a floating-point sum: every number is a function of the two matrices alone, bit for bit.  One sweep
+        of both matrices in place on the device (libsimrank_compare.so); a few numbers per node cross.  A compact or
+        loaded model is read in place; a model that still holds its plan, or is held in several column blocks
+        (``LocalWorld(P)``), is packed into one temporary block in the frame's order first: each such model costs one
+        more copy of its matrices (N^2 x 4 | 2 | 8 bytes per side) next to its plan for the length of the call, both
+        copies alive at once; ``compact()`` first where that does not fit.  Both models are left unchanged."""
+        from . import _compare
+        solver, sides = self._solver_sides()
+        if not isinstance(other, _KeptModel):
+            raise ValueError(f"other must be an estimator holding a model, not {type(other).__name__}")
+        other_solver, other_sides = other._solver_sides()
+        for which, model in (("this", self), ("the other", other)):
+            if model.kept_neighbors is not None:
+                raise ValueError(f"{which} model was pruned to kept_neighbors = {model.kept_neighbors}: it stands for a "
+                                 "different matrix P; compare before prune()")
+        _compare.check_sides(sides, other_sides)
+        tols = _compare.check_tolerances(tolerances)
+        floor = _compare.check_floor(floor)
+        k = _compare.check_top_k(top_k, [len(lab) for _, lab in sides])
+        ops, other_ops = next(iter(solver.ops.values())), next(iter(other_solver.ops.values()))
+        dev, other_dev = getattr(ops, "device", None), getattr(other_ops, "device", None)
+        if dev != other_dev:
+            raise ValueError(f"the two models live on different devices ({dev} and {other_dev})")
+        swept = tuple(sorted(set(tols) | {0.0}))
+        with contextlib.ExitStack() as scope:
+            mine = scope.enter_context(_compare.callers_readers(solver))
+            theirs = mine if other_solver is solver else scope.enter_context(_compare.callers_readers(other_solver))
+            for o in (ops, other_ops):
+                o.synchronize()                             # (the two models have streams of their own)
+            out = []
+            for s, (j, lab) in enumerate(sides):
+                got = _compare.compare_readers(mine[s], theirs[s], swept, floor, k)
+                other_ops.synchronize()
+                out.append(self._compare_frames(self._ids(j, lab, [])[0], got, swept, tols))
+        return out[0] if len(out) == 1 else tuple(out)
+
+    @staticmethod
+    def _compare_frames(index, got, swept, tols):
+        """``compare``'s three frames of one group from the arrays of ``_compare.compare_readers``."""
+        n = len(index)
+        over = got["over"].astype(np.int64)
+        label_at = lambda arg: index.take(np.maximum(arg, 0)).to_numpy() if n else np.empty(0, dtype=object)
+        cols = {"max_abs": got["max_abs"], "at": label_at(got["arg_abs"]), "max_rel": got["max_rel"],
+                "at_rel": label_at(got["arg_rel"]), "differing": over[:, swept.index(0.0)]}
+        for t in tols:
+            cols[f"over@{t!r}"] = over[:, swept.index(t)]
+        if "overlap" in got:
+            cols["overlap"], cols["same_prefix"] = got["overlap"], got["same_prefix"]
+        nodes = pd.DataFrame(cols, index=index.copy())
+        one = {"entries": np.int64(n) * np.int64(n), "differing": cols["differing"].sum(dtype=np.int64)}
+        for value, arg, node, neighbor in (("max_abs", "arg_abs", "node", "neighbor"),
+                                           ("max_rel", "arg_rel", "node_rel", "neighbor_rel")):
+            r = int(np.argmax(got[value])) if n else -1     # (the first row attaining the maximum; d and rel are never NaN)
+            one[value] = got[value][r] if n else 0.0
+            one[node] = index[r] if n else None
+            one[neighbor] = index[int(got[arg][r])] if n else None
+        for t in tols:
+            one[f"over@{t!r}"] = cols[f"over@{t!r}"].sum(dtype=np.int64)
+        if "overlap" in got:
+            one["mean_overlap"] = float(got["overlap"].sum(dtype=np.int64)) / n if n else 0.0
+            one["identical_lists"] = np.int64((got["same_prefix"] == got["k"]).sum())
+        summary = pd.DataFrame({name: [value] for name, value in one.items()})
+        histogram = pd.Series(got["hist"], index=pd.RangeIndex(len(got["hist"]), name="bin"), name="count", dtype=np.int64)
+        return summary, nodes, histogram
 
     def compact(self, precision=None):
         """Cut the kept model loose from its plan: every side's iterate is packed into ONE device matrix in the dense

@@ -1,9 +1,10 @@
-// What the companion libraries share, and nothing of the main library.  All fourteen (select, f64, query, foldin, model, sets,
-// neighbors, profile, cluster, rank, linkage, groups, kmedoids, explain) take the error plumbing of a C entry point; all but f64 and rank (which reads a
+// What the companion libraries share, and nothing of the main library.  All fifteen (select, f64, query, foldin, model, sets,
+// neighbors, profile, cluster, rank, linkage, groups, kmedoids, explain, compare) take the error plumbing of a C entry point; all but f64 and rank (which reads a
 // float64 score band, not an iterate) take the layouts a block of an iterate is read in, and what depends on them:
-//     one element      Stored<L>, offset_of<L>, load<L>, elem<L>: query, sets, neighbors, model, groups, kmedoids, explain
-//     host checks      check_block: query, sets, neighbors, model, groups, kmedoids, explain;  plan_launch: select, profile, cluster, linkage;
-//                      quad_vector_loads: sets, kmedoids
+//     one element      Stored<L>, offset_of<L>, load<L>, elem<L>: query, sets, neighbors, model, groups, kmedoids, explain,
+//                      compare
+//     host checks      check_block: query, sets, neighbors, model, groups, kmedoids, explain, compare;  plan_launch: select,
+//                      profile, cluster, linkage;  quad_vector_loads: sets, kmedoids, compare
 //     layout dispatch  with_layout, a runtime layout code as a template argument: all but model's pair dispatch
 //     the 16-byte walk Elem<L>, WALK_GEOMETRY and WALK_LOAD, the lane geometry and the load phase of a sweep: select,
 //                      profile, cluster, linkage
@@ -130,7 +131,7 @@ inline int check_block(const void* S, int32_t layout, int64_t stride, int64_t n_
 
 // Whether every quad of 4 consecutive columns c .. c + 3 (c a multiple of 4) inside the block is one aligned vector load
 // of 16 (f32), 8 (binary16) or 32 (float64) bytes: panels when the block starts on 16 (8) bytes (32 and 64 divide by 4, a
-// panel row is 128 bytes); a row-major block when its rows start on 16 bytes.  sets, kmedoids.
+// panel row is 128 bytes); a row-major block when its rows start on 16 bytes.  sets, kmedoids, compare.
 inline bool quad_vector_loads(const void* S, int32_t layout, int64_t stride) {
     const uintptr_t p = reinterpret_cast<uintptr_t>(S);
     switch (layout) {

@@ -35,7 +35,8 @@ Extra keyword-only arguments (defaults keep the reference's behaviour):
     keep              False (default) | True: hand nothing back, keep the model on the device and return the estimator
                       itself, which then answers node queries without the N x N transfer (``_kept._KeptModel``: ``rows``,
                       ``similarity``, ``most_similar``, ``fold_in`` (nodes that were NOT in the graph), ``frame``,
-                      ``top_k``, ``pairs``, ``release``; a context manager; ``compact`` cuts it down to one matrix per
+                      ``top_k``, ``pairs``, ``compare`` (how far apart two models of one graph are, measured on the
+                      device), ``release``; a context manager; ``compact`` cuts it down to one matrix per
                       side, ``save`` / ``load_model`` write it to a file and read it back).
                       One GPU or ``LocalWorld(P)``, every storage precision; not with ``top_k`` / ``min_similarity``
                       (the kept model answers them)
