@@ -35,6 +35,19 @@ def _long_frame(first, value, who, out_index, idx, val, keep_rows=None):
         value: val.ravel()[keep]})
 
 
+def _diverse_frame(first, who, out_index, idx, score, pen, val, keep_rows=None):
+    """``_long_frame`` of a diversified selection: (``first``, rank, neighbor, score) and the two float64 columns
+    ``penalty`` and ``value`` of every pick; ``rank`` is the order of picking."""
+    n, kk = idx.shape
+    keep = idx.ravel() >= 0
+    if keep_rows is not None:
+        keep &= np.repeat(np.asarray(keep_rows, dtype=bool), kk)
+    frame = _long_frame(first, "score", who, out_index, idx, score, keep_rows)
+    frame["penalty"] = pen.ravel()[keep]
+    frame["value"] = val.ravel()[keep]
+    return frame
+
+
 def _topk_frame(solver, j, k, labels):
     """Long-format hand-back: one row per (node, rank) with the k most similar OTHER nodes."""
     lab = pd.Index(labels)
@@ -198,7 +211,7 @@ class _KeptModel:
             return pd.DataFrame(solver.fold_in(j, lists, w, prior), index=new_index, columns=out_index.copy())
         return _long_frame("node", "similarity", new_index, out_index, *solver.fold_in(j, lists, w, prior, top_k=k))
 
-    def score_sets(self, sets, weights=None, names=None, group=None, top_k=None, exclude="members"):
+    def score_sets(self, sets, weights=None, names=None, group=None, top_k=None, exclude="members", diversity=None):
         """Basket queries: for each basket (a sequence of labels of FITTED nodes of ``group``, repeats counting as often
         as they occur) the row
 
@@ -212,18 +225,28 @@ class _KeptModel:
         -> DataFrame [n_sets x N] float64, columns as the dense frame's; with ``top_k=k`` the long frame (set, rank,
         neighbor, score) of the k best per basket (score descending, label position ascending), selected on the device,
         k clamped to N.  ``exclude``: "members" (the basket's own members are no candidates), None, or one sequence of
-        labels per basket that are no candidates instead; a basket with fewer than k candidates gets fewer rows."""
-        from . import _sets
+        labels per basket that are no candidates instead; a basket with fewer than k candidates gets fewer rows.
+
+        ``diversity=d`` (with ``top_k``; a real number in [0, 1]): the k are picked one by one on the device by maximal
+        marginal relevance instead.  Every remaining candidate b carries ``penalty(b)``, the largest ``S[p, b]`` over
+        the picks p made so far (row p of the group's matrix; +0.0 before the first pick and never below it), and the
+        next pick is the candidate with the greatest ``value = ((1 - d) * score) - (d * penalty)``, three float64
+        operations, ties by label position.  -> the long frame (set, rank, neighbor, score, penalty, value), ``rank`` the
+        order of picking.  ``d = 0`` picks what ``top_k`` alone does."""
+        from . import _diverse, _sets
         solver, j, labels = self._kept(group)
+        d = _diverse.check_diversity(diversity, top_k)
         index, _ = self._ids(j, labels, [])
         ptr, ids, w, names, k, excl = _sets.prepare(sets, index, weights=weights, names=names, top_k=top_k,
                                                     exclude=exclude)
         who = pd.RangeIndex(ptr.size - 1) if names is None else pd.Index(names)
+        if d is not None:
+            return _diverse_frame("set", who, index, *solver.score_diverse(j, ptr, ids, w, k, excl, d))
         if k is None:
             return pd.DataFrame(solver.score_sets(j, ptr, ids, w), index=who, columns=index.copy())
         return _long_frame("set", "score", who, index, *solver.score_sets(j, ptr, ids, w, k, excl))
 
-    def recommend(self, nodes, k, group=None, exclude_seen=True):
+    def recommend(self, nodes, k, group=None, exclude_seen=True, diversity=None):
         """Leg 1 of the update for chosen rows: for each fitted node u of ``group`` the k best of ``(W . S)[u, :]``, the
         scores of u's neighbours' rows (its in-neighbours for the directed classes; for the bipartite classes the
         group-2 neighbours of a group-1 node, read from group 2's matrix, and the other way round), every weight
@@ -231,15 +254,21 @@ class _KeptModel:
         ``exclude_seen``: u's neighbours (and, for the directed classes, u itself) are no candidates.
 
         -> long frame (node, rank, neighbor, score), blocks in the order of ``nodes``; ``neighbor`` is a node of the
-        group the basket lives in.  A node without neighbours gets no rows."""
-        from . import _sets
+        group the basket lives in.  A node without neighbours gets no rows.  ``diversity=d``: the k picked by maximal
+        marginal relevance as ``score_sets(diversity=d)`` picks them, the penalties read from the matrix the baskets live
+        in -> (node, rank, neighbor, score, penalty, value)."""
+        from . import _diverse, _sets
         solver, side, j, index, src_j, src_index = self._across(group)
         if not isinstance(exclude_seen, bool):
             raise ValueError(f"exclude_seen must be True or False, not {exclude_seen!r}")
+        d = _diverse.check_diversity(diversity, k)
         k = _sets.check_top_k(k, len(src_index))
         _, ids = self._ids(j, index, nodes)
         spec = solver.specs[side]
         ptr, members, w, excl = _sets.csr_baskets(spec.csr, spec.rowscale, ids, src_j == j, exclude_seen)
+        if d is not None:
+            return _diverse_frame("node", index.take(ids), src_index,
+                                  *solver.score_diverse(src_j, ptr, members, w, k, excl, d), keep_rows=np.diff(ptr) > 0)
         idx, val = solver.score_sets(src_j, ptr, members, w, k, excl)
         return _long_frame("node", "score", index.take(ids), src_index, idx, val, keep_rows=np.diff(ptr) > 0)
 

@@ -274,6 +274,12 @@ class NeighborSolver(SolverQueries):
         self._reader(j)                                      # (raises when the tables were released)
         return self.tables[j].host()
 
+    def score_diverse(self, j, ptr, ids, w, k, excl, d, timing=None):
+        """``SolverQueries.score_diverse`` for the matrix P, on the device: the band from ``score_band``, the picks from
+        ``simrank_diverse_pick_lists`` on the tables."""
+        from . import _diverse
+        return _diverse.run(self._reader(j), ptr, ids, w, k, excl, d, timing)
+
     def pairs(self, j, t, max_pairs):
         """Side j's kept off-diagonal entries at least ``t``: (offsets [n + 1], neighbour ids ascending within a node,
         values), on the host after one copy of the tables."""

@@ -161,6 +161,14 @@ class SolverQueries:
         from . import _rank
         return _rank.run(self._reader(j), ptr, ids, w, excl, tptr, tids, timing)
 
+    def score_diverse(self, j, ptr, ids, w, k, excl, d, timing=None):
+        """The k picks per basket at diversity ``d`` on side j's iterate (``_diverse.run``): the baskets as ``score_sets``
+        takes them -> (ids int32, score, penalty, value float64), each [n_sets, k]; the score band stays on the device.
+        A side held in several column blocks is first packed into one (``one_block``)."""
+        from . import _diverse
+        with self.one_block(j) as reader:
+            return _diverse.run(reader, ptr, ids, w, k, excl, d, timing)
+
     def _close_readers(self):
         folders, self._folders = self._folders or {}, None
         for f in folders.values():
