@@ -246,6 +246,63 @@ class _KeptModel:
             return pd.DataFrame(solver.score_sets(j, ptr, ids, w), index=who, columns=index.copy())
         return _long_frame("set", "score", who, index, *solver.score_sets(j, ptr, ids, w, k, excl))
 
+    def matmul(self, X, transpose=False, group=None):
+        """The model as a linear operator: ``S @ X`` of the group's matrix (``transpose=True``: ``S.T @ X``; the matrices
+        are not symmetric in general), every element widened as ``rows`` widens it, products and sums in float64.
+
+        ``X``: a DataFrame or Series indexed by the group's fitted labels, in any order, every node exactly once (as
+        ``cluster_quality`` takes ``labels``), or an array-like of shape [N] or [N, d] in the dense frame's order; real
+        floating or integer data, finite or not (bool, object and complex dtypes are a ValueError, an unknown label a
+        KeyError), checked before any device work.
+
+        -> DataFrame [N x d] float64, indexed by the dense frame's labels in its order, with ``X``'s columns (a
+        ``RangeIndex`` for an array); a Series or a 1-D array in gives a Series.
+
+        The matrix is read in place on the device (libsimrank_operator.so), once per band of 64 columns; ``X`` and the
+        result cross PCIe once.  The order of a sum's additions depends on the shape alone and there are no
+        floating-point atomics: two calls give the same bits, and every element lies within ``N * 2^-52 * sum |S| |X|``
+        of the exact one.  A model held in several column blocks (``LocalWorld(P)``) is packed into one temporary block
+        first; a pruned model is answered on the host for its matrix P, whose absent entries are +0.0 and add nothing.
+        The model is left unchanged."""
+        from . import _operator
+        solver, j, labels = self._kept(group)
+        if not isinstance(transpose, (bool, np.bool_)):
+            raise ValueError(f"transpose must be True or False, not {transpose!r}")
+        index, _ = self._ids(j, labels, [])
+        dense, columns, kind, name = _operator.check_operand(X, index)
+        out = solver.apply_operator(j, dense, bool(transpose))
+        if kind in ("series", "vector"):
+            return pd.Series(out[:, 0], index=index.copy(), name=name)
+        return pd.DataFrame(out, index=index.copy(), columns=columns)
+
+    def embed(self, dim, oversample=8, power_iterations=2, seed=0, group=None):
+        """Vectors for the nodes: the spectral embedding of the symmetric part ``M = (S + S.T) / 2`` of the group's
+        matrix by a randomized subspace iteration.  With ``p = min(dim + oversample, N)``:
+
+            Q = qr(default_rng(seed).standard_normal((N, p)))[0]
+            repeat power_iterations times:  Q = qr(M @ Q)[0]
+            Y = M @ Q;  B = Q.T @ Y;  B = (B + B.T) / 2;  w, Z = eigh(B)
+            the dim largest w, descending;  V = Q @ Z[:, those]
+
+        and every column of V gets the sign that makes its entry of largest magnitude (the first on a tie) positive.
+        ``dim``: an int in 1 .. N; ``oversample``: an int >= 0; ``power_iterations``: an int in 0 .. 16; ``seed``: a
+        non-negative int (each a ValueError before any device work).
+
+        -> ``(vectors, eigenvalues)``: a DataFrame [N x dim] float64 indexed by the dense frame's labels in its order,
+        orthonormal columns; a float64 Series of length ``dim``, ``eigenvalues[i] = v_i.T M v_i``.
+
+        ``M @ Q`` is two products of ``matmul``'s kernel on the device, ``0.5 S Q`` and ``+ 0.5 S.T Q`` where the first
+        result lies; per product Q goes up and Y (N x p x 8 bytes) comes down for the host's QR.  The same call gives
+        the same bits twice.  Where ``matmul`` runs, and as it does.  The model is left unchanged."""
+        from . import _operator
+        solver, j, labels = self._kept(group)
+        index, _ = self._ids(j, labels, [])
+        dim, p, iters, seed = _operator.check_embed_args(dim, oversample, power_iterations, seed, len(index))
+        V, w = solver.embed_operator(j, dim, p, iters, seed)
+        cols = pd.RangeIndex(dim)
+        return (pd.DataFrame(V, index=index.copy(), columns=cols),
+                pd.Series(w, index=cols.copy(), name="eigenvalue", dtype=np.float64))
+
     def recommend(self, nodes, k, group=None, exclude_seen=True, diversity=None):
         """Leg 1 of the update for chosen rows: for each fitted node u of ``group`` the k best of ``(W . S)[u, :]``, the
         scores of u's neighbours' rows (its in-neighbours for the directed classes; for the bipartite classes the

@@ -169,6 +169,28 @@ class SolverQueries:
         with self.one_block(j) as reader:
             return _diverse.run(reader, ptr, ids, w, k, excl, d, timing)
 
+    def apply_operator(self, j, X, transpose=False, timing=None):
+        """Side j's matrix as a linear operator (``_operator.product``): ``S @ X``, or ``S.T @ X``, for the host float64
+        [n, d] block ``X`` in the caller's order -> float64 [n, d].  A side held in several column blocks is first packed
+        into one (``one_block``); a pruned model is answered on the host for its matrix P (``lists``)."""
+        from . import _operator
+        lists = self.lists(j)
+        if lists is not None:
+            return _operator.product_lists(*lists, X, transpose)
+        with self.one_block(j) as reader:
+            return _operator.product(reader, X, transpose, timing)
+
+    def embed_operator(self, j, dim, p, power_iterations, seed, timing=None):
+        """The spectral embedding of the symmetric part of side j's matrix (``_operator.embed``) -> (V float64 [n, dim],
+        eigenvalues float64 [dim]); where ``apply_operator`` runs, and as it does."""
+        from . import _operator
+        lists = self.lists(j)
+        if lists is not None:
+            sym = lambda Q: 0.5 * _operator.product_lists(*lists, Q) + 0.5 * _operator.product_lists(*lists, Q, True)
+            return _operator.embed_host(sym, self.n[j], dim, p, power_iterations, seed)
+        with self.one_block(j) as reader:
+            return _operator.embed(reader, dim, p, power_iterations, seed, timing)
+
     def _close_readers(self):
         folders, self._folders = self._folders or {}, None
         for f in folders.values():
