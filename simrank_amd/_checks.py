@@ -1,5 +1,5 @@
 """The two scalar predicates the argument checks of the companion bindings share (``_query``, ``_explain``, ``_groups``,
-``_kmedoids``, ``_linkage``, ``_profile``, ``_cluster``).  Every message stays with the check that raises it, except the one
+``_kmedoids``, ``_linkage``, ``_profile``, ``_cluster``, ``_density``).  Every message stays with the check that raises it, except the one
 message that three checks share word for word (``finite``).  Nothing here touches a device.
 """
 from __future__ import annotations

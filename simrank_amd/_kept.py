@@ -557,6 +557,58 @@ class _KeptModel:
             return pd.DataFrame(labels.T.reshape(len(index), len(ts)), index=index, columns=[float(x) for x in ts], dtype=np.int64)
         return self._all_sides(make)
 
+    def degrees(self, t):
+        """How many neighbours every node has at threshold ``t``: two different nodes a, b are neighbours iff
+        ``S[a, b] >= t`` or ``S[b, a] >= t``, the relation of ``components`` (float64 on the bits the dense frame holds;
+        NaN never passes, -0.0 >= 0.0 does); a pair that passes in both directions is one neighbour.  ``t``: one finite
+        number -> a Series "neighbors" (int64) over the dense frame's labels in its order; a sequence of 1 to 8 numbers
+        of any sign, in any order, repeats allowed -> a DataFrame with one such column per threshold, labelled
+        ``float(t)``, in the order given.  One sweep of the iterate in place for all thresholds, every element read once
+        (libsimrank_density.so: entry (a, b) meets entry (b, a) in the workgroup that holds both of their tiles); a side
+        held in several column blocks is packed into one temporary block first.  A pruned model is answered on the host
+        for its matrix P and needs ``t > 0``: its absent entries are +0.0 and would make everybody everybody's neighbour.
+        The model is left unchanged.  A tuple of two for the bipartite classes."""
+        from . import _density
+        ts, scalar = _density.check_thresholds(t)
+        _density.check_solver(self._solver_sides()[0], ts)
+
+        def make(solver, j, lab):
+            deg = _density.degrees(solver, j, ts)
+            index = pd.Index(lab)
+            if scalar:
+                return pd.Series(deg[0], index=index, name="neighbors", dtype=np.int64)
+            return pd.DataFrame(deg.T.reshape(len(index), len(ts)), index=index, columns=[float(x) for x in ts], dtype=np.int64)
+        return self._all_sides(make)
+
+    def dbscan(self, t, min_samples=5):
+        """Density clusters (DBSCAN) at threshold ``t`` (one finite number) over the neighbours of ``degrees(t)``.
+
+        -> DataFrame over the dense frame's labels in its order: ``neighbors`` (int64) is ``degrees(t)``; ``core`` (bool)
+        is ``neighbors + 1 >= min_samples``: the node counts itself, as scikit-learn's ``DBSCAN`` counts it
+        (``min_samples``: an int >= 1); ``cluster`` (int64): two core nodes that are neighbours are in one cluster,
+        transitively; a node that is not core but has a core neighbour is a border node and takes the cluster of its
+        FIRST core neighbour in the frame's order (classical DBSCAN leaves that to the scan order; here it is a function
+        of the matrix alone); every other node is noise, -1.  Border nodes never extend a cluster: two core nodes that
+        share only a border node stay apart.  Clusters are numbered 0, 1, 2, ... in the order of their first member,
+        core or border, as ``components`` numbers: ``dbscan(t, 1).cluster`` is ``components(t)``.
+
+        Three sweeps on the device (libsimrank_density.so): the counts, a lock-free union-find over the core nodes on
+        integer atomics with an atomic minimum for the border nodes, and the labels; 8 N bytes cross.  Runs where
+        ``degrees`` runs, and as it does (a pruned model: ``t > 0``).  The model is left unchanged.  A tuple of two for
+        the bipartite classes."""
+        from . import _density
+        ts, scalar = _density.check_thresholds(t)
+        if not scalar:
+            raise ValueError(f"dbscan takes one threshold, a finite number, not {t!r}")
+        min_neighbors = _density.check_min_samples(min_samples)
+        _density.check_solver(self._solver_sides()[0], ts)
+
+        def make(solver, j, lab):
+            deg, labels = _density.dbscan(solver, j, float(ts[0]), min_neighbors)
+            return pd.DataFrame({"cluster": _density.number(labels), "core": deg >= min_neighbors, "neighbors": deg},
+                                index=pd.Index(lab))
+        return self._all_sides(make)
+
     def linkage(self, min_similarity=None):
         """The single-linkage dendrogram: every ``components(t)`` at once.  Two different nodes a, b fall together at the
         height ``w(a, b) = max(S[a, b], S[b, a])``, compared as ``components`` compares (float64 on the bits the dense frame
