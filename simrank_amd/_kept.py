@@ -609,7 +609,59 @@ class _KeptModel:
                                 index=pd.Index(lab))
         return self._all_sides(make)
 
-    def linkage(self, min_similarity=None):
+    def core_similarity(self, min_samples=5):
+        """Every node's core similarity: the (``min_samples`` - 1)-th largest of its pair heights
+        ``w(a, b) = max(S[a, b], S[b, a])``, b != a, compared as ``components`` compares (float64 on the bits the dense
+        frame holds; a NaN entry is no entry, -0.0 and +0.0 are one value, +0.0).  The node counts itself, as ``dbscan``
+        counts (``min_samples``: an int >= 1): +inf at ``min_samples=1``, -inf for a node with fewer pairs.  It is a
+        selection, hence exact, and ``core_similarity(m) >= t`` iff ``dbscan(t, m).core`` for every finite t: sorted, it
+        is the k-distance plot from which a ``t`` for ``dbscan`` is read.
+
+        -> Series "core_similarity" (float64) over the dense frame's labels in its order.  A radix select on the device
+        (libsimrank_hdbscan.so) that pairs entry (a, b) with entry (b, a) as ``degrees`` does: 8 sweeps of an f32 model,
+        4 of an fp16-held and 16 of a float64 one, whatever N and ``min_samples``; 8 N bytes cross.  Runs where
+        ``degrees`` runs; a pruned model is answered on the host for its matrix P, whose absent entries are +0.0.  The
+        model is left unchanged.  A tuple of two for the bipartite classes."""
+        from . import _hdbscan
+        rank = _hdbscan.check_min_samples(min_samples)
+        return self._all_sides(lambda solver, j, lab: pd.Series(
+            _hdbscan.core_similarity(solver, j, rank), index=pd.Index(lab), name="core_similarity", dtype=np.float64))
+
+    def hdbscan(self, min_cluster_size=5, min_samples=None, min_similarity=None, selection="eom",
+                allow_single_cluster=False):
+        """HDBSCAN*: clusters of different density, read off ``linkage(min_samples=m)`` by host arithmetic, with the
+        similarity itself as the density level (no distance, no division).  ``min_cluster_size``: an int >= 2;
+        ``min_samples``: an int >= 1, by default ``min_cluster_size``; ``min_similarity`` as ``linkage``'s;
+        ``selection``: "eom" or "leaf".
+
+        The hierarchy is the multi-way one the table encodes: a class is a component of some ``cut(Z, t)``, its children
+        the classes (or leaves) of the next higher level inside it; a class without a parent is a root.  Condensing runs
+        top-down from every root of at least ``min_cluster_size`` nodes, whose cluster is born at the height the root
+        forms.  At a class of the current cluster C that forms at h: two or more children of at least
+        ``min_cluster_size`` nodes end C, and each starts a cluster born at h; exactly one continues C; the members of
+        every other child leave C at h.  ``stability(C)`` is the exactly rounded sum of ``leave(p) - birth(C)`` over the
+        nodes p of C at its birth.  "eom", bottom-up: a cluster without child clusters is selected with its stability as
+        score; another one is selected instead of its descendants when its stability is at least the sum of its
+        children's scores and it is no root (or ``allow_single_cluster``); otherwise its score is that sum.  "leaf": the
+        clusters without child clusters, a root only with ``allow_single_cluster``.
+
+        -> (labels, clusters).  ``labels``: a DataFrame over the dense frame's labels: ``cluster`` (int64), the selected
+        cluster that held the node at its birth, numbered 0, 1, ... by first member, -1 for noise, and
+        ``core_similarity`` (float64).  ``clusters``: one row per cluster of the condensed tree, ordered by (smallest
+        member, size descending): ``parent`` (the row, or -1), ``birth``, ``size`` at birth, ``stability``, ``selected``,
+        ``cluster`` (the label, or -1).  A function of the matrix alone, ties included.  Runs where ``linkage`` runs.
+        A tuple of two such pairs for the bipartite classes."""
+        from . import _hdbscan, _linkage
+        mcs, rank, floor = _hdbscan.check_hdbscan(min_cluster_size, min_samples, min_similarity, selection)
+        _linkage.check_solver(self._solver_sides()[0], floor)
+
+        def make(solver, j, lab):
+            n, core, left, right, sim, size = _hdbscan.table(solver, j, rank, floor)
+            labels, clusters = _hdbscan.condense(n, left, right, sim, size, mcs, selection, bool(allow_single_cluster))
+            return (pd.DataFrame({"cluster": labels, "core_similarity": core}, index=pd.Index(lab)), pd.DataFrame(clusters))
+        return self._all_sides(make)
+
+    def linkage(self, min_similarity=None, min_samples=None):
         """The single-linkage dendrogram: every ``components(t)`` at once.  Two different nodes a, b fall together at the
         height ``w(a, b) = max(S[a, b], S[b, a])``, compared as ``components`` compares (float64 on the bits the dense frame
         holds); a NaN entry is no entry, -0.0 and +0.0 are one height, reported as +0.0.
@@ -629,12 +681,26 @@ class _KeptModel:
         ceil(log2 N) + 1 rounds, each one sweep of the iterate in place (two for a float64 model), integer atomics only;
         12 N bytes cross, and the host orders the N - 1 edges.  A pruned model is answered on the host from its lists and
         needs ``min_similarity > 0``: its absent entries are +0.0 and tie everything at 0.  The model is left unchanged.
-        A tuple of two for the bipartite classes."""
+        A tuple of two for the bipartite classes.
+
+        ``min_samples=m`` (an int >= 1) gives the same table of the MUTUAL REACHABILITY
+        ``min(w(a, b), core_m(a), core_m(b))`` with ``core_m = core_similarity(m)``, a pair at -inf being no entry:
+        HDBSCAN*'s hierarchy, which chains less through sparse nodes.  ``cut(Z, t=t)`` of it leaves every node that is
+        not core in ``dbscan(t, m)`` alone and parts the core nodes as ``dbscan(t, m).cluster`` does; ``m = 1`` is the
+        plain table.  One select (``core_similarity``) and the same rounds with the clamped pick of
+        libsimrank_hdbscan.so, on the one block ``degrees`` reads.  None takes exactly the path above."""
         from . import _linkage
         floor = _linkage.check_floor(min_similarity)
+        rank = None
+        if min_samples is not None:
+            from . import _hdbscan
+            rank = _hdbscan.check_min_samples(min_samples)
         _linkage.check_solver(self._solver_sides()[0], floor)
 
         def make(solver, j, lab):
+            if rank is not None:
+                _, _, left, right, sim, size = _hdbscan.table(solver, j, rank, floor)
+                return pd.DataFrame(dict(zip(_linkage.COLUMNS, (left, right, sim, size))))
             _, left, right, sim, size = _linkage.table(solver, j, floor)
             return pd.DataFrame(dict(zip(_linkage.COLUMNS, (left, right, sim, size))))
         return self._all_sides(make)

@@ -100,18 +100,29 @@ def max_rounds(n: int) -> int:
     return (max(1, n) - 1).bit_length() + 1
 
 
-def forest_blocks(ops, blocks, n: int, floor, timing=None):
+def _plain_pick(lib):
+    """Today's pick: ``simrank_linkage_pick`` on a block dict."""
+    def pick(b, floor_ref, phase, comp, best, n, status, stream):
+        check(lib.simrank_linkage_pick(b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], b.get("row_ids"),
+                                       b.get("col_ids"), floor_ref, phase, comp, best, n, status, stream), "simrank_linkage_pick")
+    return pick
+
+
+def forest_blocks(ops, blocks, n: int, floor, timing=None, pick=None):
     """(a int64, b int64, value float64, rounds): a maximum spanning forest of w(a, b) = max(S[a, b], S[b, a]) over
     ``blocks`` (dicts with ptr, layout, stride, rows, cols and optional device row_ids / col_ids naming ids 0 .. n - 1),
     as edges between node ids with the value they join at, and the number of rounds run.  ``floor``: None or a float;
     entries below it are not used.  One ``simrank_linkage_pick`` per block and round (two for a float64 iterate), all
     into one array of slots.  ``timing``: a list or dict that receives the milliseconds of each stage (HIP events).
+    ``pick``: what queues one pick, ``pick(block, floor_ref, phase, comp, best, n, status, stream)``; None is
+    ``simrank_linkage_pick`` (``_hdbscan`` passes the pick that clamps every entry by two core similarities).
     LinkageError when the device status word is not 0 or the rounds pass ``max_rounds(n)``."""
     assert n >= 1 and len(blocks) >= 1
     layouts = {b["layout"] for b in blocks}
     wide = ROWMAJOR_F64 in layouts
     assert len({lay == ROWMAJOR_F64 for lay in layouts}) == 1, "the blocks of one iterate hold one type"
     lib = load()
+    pick = pick or _plain_pick(lib)
     phases = 2 if wide else 1                                # (float64: the key, then the root; simrank_linkage_phases)
     if floor is None:
         floor_ref = None
@@ -132,9 +143,7 @@ def forest_blocks(ops, blocks, n: int, floor, timing=None):
             rounds += 1
             for phase in range(phases):
                 for b in blocks:
-                    stage(ops, timing, "pick_ms", lambda: check(lib.simrank_linkage_pick(
-                        b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], b.get("row_ids"), b.get("col_ids"), floor_ref,
-                        phase, comp, best, n, status, ops.stream), "simrank_linkage_pick"))
+                    stage(ops, timing, "pick_ms", lambda: pick(b, floor_ref, phase, comp, best, n, status, ops.stream))
             stage(ops, timing, "hook_ms", lambda: check(lib.simrank_linkage_hook(
                 best, 64 if wide else 32, comp, hook_other, hook_value, n, state, status, ops.stream), "simrank_linkage_hook"))
             stage(ops, timing, "flatten_ms", lambda: check(lib.simrank_linkage_flatten(comp, best, n, status, ops.stream),
