@@ -19,6 +19,9 @@ of two it stays exact.  ``kind="wide"``: many binades, with (f32 layouts) values
 round-to-nearest-even ties, +0 and -0 and the largest values that still fit; values the form cannot hold only when
 ``overflow=n`` asks for n of them.
 
+``make_long`` builds the blocks with one LONG dimension (tens of thousands of rows or columns) that ``make_block`` cannot:
+the same dyadic values drawn with repeats, for the tests in which one workgroup takes several turns.
+
 The references below are written for reading, not for speed; tests/test_blocks_cpu.py pins them and the generator.
 """
 from fractions import Fraction
@@ -253,6 +256,38 @@ def check_block(blk, overflow=0):
     assert (sq[off] != sq.T[off]).all()
     for r, c2, c1 in blk.repeats:
         assert A[r, c2] == A[r, c1]
+
+
+def make_long(layout, n_rows, n_cols, stride, seed, *, zero_fraction=0.04):
+    """-> ``Block``: a block with one LONG dimension (tens of thousands of rows or of columns), which ``make_block`` cannot
+    build: its pool has 8 190 values, it wants one per row and per column and deals the rows in a Python loop.  The
+    logical matrix is drawn, with repeats, from the same dyadic pool (both signs, every value exactly storable), about
+    ``zero_fraction`` of it exact zeros; padding holds the layout's dyadic sentinel.  Rows and columns are NOT distinct:
+    use it where the reference has an exact tie rule.  ``repeats`` is empty; ``check_long`` asserts the rest."""
+    assert layout in LAYOUTS and n_rows >= 1 and n_cols >= 1
+    rng = np.random.default_rng([seed, layout, n_rows, n_cols, 2])
+    pool = _pool(layout, "dyadic", rng, 0)
+    A = pool[rng.integers(0, pool.size, size=(n_rows, n_cols))]
+    A[rng.random((n_rows, n_cols)) < zero_fraction] = 0.0
+    blk = Block(layout, A, stride, SENTINEL[(layout, "dyadic")], np.argwhere(A == 0),
+                np.zeros((0, 3), dtype=np.int64), {})
+    check_long(blk)
+    return blk
+
+
+def check_long(blk):
+    """What ``make_long`` promises, asserted: the stored block decodes to A bit for bit (so every value is exactly storable),
+    everything the addressing does not reach holds the sentinel, the sentinel is above every value, both signs and zeros."""
+    A, (n_rows, n_cols) = blk.A, blk.A.shape
+    at = offsets(blk.layout, n_rows, n_cols, blk.stride).ravel()
+    assert np.array_equal(bits(widen(blk.layout, blk.stored[at])), bits(A.ravel()))
+    assert np.isfinite(A).all() and (np.abs(A) < blk.sentinel).all()
+    pad = np.ones(blk.stored.size, dtype=bool)
+    pad[at] = False
+    assert pad.sum() == blk.stored.size - A.size                          # an injective addressing
+    assert (bits(blk.stored[pad]) == bits(store(blk.layout, blk.sentinel).reshape(1))[0]).all()
+    if A.size >= 200:
+        assert (A > 0).any() and (A < 0).any() and len(blk.zeros)
 
 
 # ---- query ----------------------------------------------------------------------------------------------------------

@@ -125,3 +125,47 @@ def assert_exact(A, X, alpha=1.0, beta=0.0, out0=None):
         o = np.abs(np.asarray(out0, dtype=np.float64)) * 4096.0
         assert np.array_equal(o, np.round(o))
         assert (abs(alpha) * steps.astype(np.float64) + abs(beta) * o).max() * 4 < 2.0 ** 52
+
+
+# ---- shapes at which one workgroup walks SEVERAL tiles of the contraction -------------------------------------------------
+# operator.hip cuts the contraction into parts = min(ceil(1536 / strips), tiles, 64) and gives a workgroup
+# tiles_per_part = ceil(tiles / parts) tiles: one, unless tiles > 64.  These are the smallest shapes past that, per kernel:
+# (kernel, n_rows, n_cols, transpose, the d's it is run at, output rows per strip, contraction steps per tile).
+LONG_CASES = [
+    ("product, TQ = 4", 131, 2130, 0, (9, 32), 128, 32),
+    ("product, TQ = 8", 131, 2130, 0, (33, 64), 128, 32),
+    ("product, TQ = 8", 5, 4200, 0, (33, 64), 128, 32),
+    ("product, transposed", 2130, 131, 1, (9, 64), 128, 32),
+    ("product, transposed", 4200, 5, 1, (9, 64), 128, 32),
+    ("rows", 20, 16700, 0, (1, 8), 16, 256),
+    ("rows", 20, 33000, 0, (1, 8), 16, 256),
+    ("rows", 20, 16400, 0, (1, 8), 16, 256),            # 65 tiles in parts of 2: the one rows shape with a short last part
+    ("cols", 4200, 9, 1, (1, 8), 1024, 64),
+    ("cols", 8300, 40, 1, (1, 8), 1024, 64),
+]
+LONG_IDS = ["%s %dx%d" % (c[0].replace(",", "").replace(" ", "_").replace("=", ""), c[1], c[2]) for c in LONG_CASES]
+
+
+def split_of(lib, case, d):
+    """(tiles, parts, tiles per part, tiles of the last part) of a LONG_CASES entry at d: the parts from the library, the
+    tiles from the mirrored depth."""
+    _, n_rows, n_cols, transpose, _, _, depth = case
+    n_in = n_rows if transpose else n_cols
+    tiles = -(-n_in // depth)
+    parts = lib.simrank_operator_parts(n_rows, n_cols, transpose, d)
+    assert 1 <= parts <= tiles
+    per = -(-tiles // parts)
+    return tiles, parts, per, tiles - (parts - 1) * per
+
+
+def assert_long_cases_walk_several_tiles(lib):
+    """Every case has a workgroup that takes at least two tiles, its last part is not empty, and every kernel has one case
+    whose last part is shorter than the others: a change to the split makes this fail instead of quietly going back to
+    one tile per part."""
+    short = {}
+    for case in LONG_CASES:
+        for d in case[4]:
+            tiles, parts, per, last = split_of(lib, case, d)
+            assert per >= 2 and 1 <= last <= per, (case, d, tiles, parts, per, last)
+            short[case[0]] = short.get(case[0], False) or last < per
+    assert short and all(short.values()), short

@@ -32,6 +32,41 @@ def test_blocks_round_trip_and_keep_their_promises(layout, kind):
     assert B.make_block(layout, 9, 63, 70, 4, kind=kind).raw != B.make_block(layout, 9, 63, 70, 5, kind=kind).raw
 
 
+LONG = [(65545, 40), (24577, 40), (20, 33000), (8300, 40), (5, 4200)]      # the tall and long shapes of the GPU tests
+
+
+@pytest.mark.parametrize("layout", B.LAYOUTS)
+def test_long_blocks_round_trip_and_keep_their_promises(layout):
+    """``make_long`` at the shapes ``make_block`` cannot reach: decode(encode(A)) == A bit for bit, padding holds the
+    sentinel, every value exactly storable, both signs, about 4 % zeros, the seed decides everything."""
+    for n_rows, n_cols in LONG:
+        for tag, stride, _ in B.variants(layout, n_rows, n_cols)[-2:]:
+            blk = B.make_long(layout, n_rows, n_cols, stride, 3)                       # (asserts its promises itself)
+            A = blk.A
+            assert A.dtype == np.float64 and A.shape == (n_rows, n_cols)
+            assert len(blk.raw) == B.n_elems(layout, n_rows, n_cols, stride) * np.dtype(B.STORED[layout]).itemsize
+            back = B.decode(layout, blk.raw, n_rows, n_cols, stride)
+            assert np.array_equal(B.bits(back), B.bits(A)), (tag, n_rows, n_cols)
+            assert np.array_equal(B.bits(B.encode(layout, back, stride, blk.sentinel)), B.bits(blk.stored))
+            assert np.array_equal(B.bits(B.store(layout, A).astype(np.float64)),
+                                  B.bits(A * (B.HALF_SCALE if layout == B.PANEL_F16 else 1.0)))
+            pad = np.ones(blk.stored.size, dtype=bool)
+            pad[B.offsets(layout, n_rows, n_cols, stride).ravel()] = False
+            assert pad.any() and (B.widen(layout, blk.stored[pad]) == blk.sentinel).all()
+            assert blk.sentinel == B.SENTINEL[(layout, "dyadic")] and (np.abs(A) < blk.sentinel).all()
+            steps = A * 1024.0
+            assert np.array_equal(steps, np.round(steps)) and np.abs(A).max() < 16     # what operator_ref.assert_exact needs
+            assert (A > 0).mean() > 0.4 and (A < 0).mean() > 0.4
+            assert 0.03 < (A == 0).mean() < 0.05 and len(blk.zeros) == (A == 0).sum()
+            # every stretch of 8 rows (a wave of a panel sweep) and every column holds both signs
+            if n_cols >= 40:
+                assert (A > 0).any(axis=1).all() and (A < 0).any(axis=1).all()
+    same = B.make_long(layout, 8197, 40, B.variants(layout, 8197, 40)[0][1], 4)
+    again = B.make_long(layout, 8197, 40, same.stride, 4)
+    other = B.make_long(layout, 8197, 40, same.stride, 5)
+    assert same.raw == again.raw and same.raw != other.raw
+
+
 def test_the_addressing_is_the_headers():
     """Hand-computed offsets of include/simrank_query.h's formulas."""
     assert B.offsets(B.PANEL_F32, 5, 70, 9)[4, 69] == ((69 >> 5) * 9 + 4) * 32 + (69 & 31) == (2 * 9 + 4) * 32 + 5

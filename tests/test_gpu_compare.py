@@ -5,7 +5,9 @@ above every value, which a kernel that counted padding would report as a differe
 (what ``compact(precision="fp16")`` does to an f32 model) with a seeded fraction of elements perturbed: one-ulp changes,
 sign-of-zero flips, NaN and +-inf planted on one side or on both, and one row whose maximum occurs twice.  All 16 layout
 pairs; every shape of ``blocks.SHAPES`` and every stride / base of ``blocks.variants`` on four pairs; n_tol = 0, 1 and 8;
-the histogram ADDED to a non-zero pattern; guard elements after every output; one 3000 x 1025 all-equal block.
+the histogram ADDED to a non-zero pattern; guard elements after every output; one 3000 x 1025 all-equal block; and
+8 197 x 40 and 24 577 x 40 blocks of ``blocks.make_long`` on six pairs: more rows than the capped grid has waves, so a
+wave takes a second, third and fourth row.
 
 Model level, on a 600-node directed graph (the generator of tests/test_gpu_neighbors.py at a size whose N - 1 neighbours
 ``most_similar`` still lists) and that module's bipartite graph: ``compare`` equals
@@ -222,6 +224,90 @@ def test_an_all_equal_block_of_many_rows(dev):
     for g, w, name in zip(got, expected(ref, n_rows, 8), NAMES):
         same_bits(g, w, ("all equal", name))
     assert got[1][1234] == 77 and got[1][0] == 0
+
+
+# ---- 1b. past the grid cap: a wave takes a second, third and fourth row ------------------------------------------------------
+TURN = 2048 * 4                                         # SIMRANK_COMPARE_MAX_GRID workgroups of four waves, one row per wave
+TALL = (8197, 24577)                                    # a second turn of five rows; four turns, the last of ONE row
+TALL_PAIRS = [(l, l) for l in B.LAYOUTS] + [(B.ROWMAJOR_F32, B.PANEL_F16), (B.ROWMAJOR_F64, B.PANEL_F32)]
+
+
+def tall_pair(la, lb, n_rows, n_cols, seed):
+    """(MA, MB, equal rows): stored elements of two tall blocks.  Both are ``blocks.make_long``'s values (the binary16
+    pool where either side is binary16, so that both casts are exact); about one element in twenty of B is then changed:
+    one ulp up or down, a flipped sign of zero, NaN on one side or on both, an infinity.  One row of every turn of more
+    than three rows is equal throughout (its answer is (0.0, column 0) and all its elements are zeros of the histogram);
+    the first and the last row of every turn differ."""
+    base = B.PANEL_F16 if B.PANEL_F16 in (la, lb) else la
+    V = B.make_long(base, n_rows, n_cols, n_rows + 3 if base in B.PANEL else n_cols + 4, seed).A
+    MA, MB = cast(la, V), cast(lb, V)
+    assert np.array_equal(B.widen(la, MA), V) and np.array_equal(B.widen(lb, MB), V)
+    rng = np.random.default_rng([seed, la, lb, n_rows])
+    turns = [(lo, min(lo + TURN, n_rows)) for lo in range(0, n_rows, TURN)]
+    equal = np.array([lo + min(5 + 3 * t, hi - lo - 2) for t, (lo, hi) in enumerate(turns) if hi - lo > 3])   # (no two one turn apart)
+    ends = np.array([r for lo, hi in turns for r in (lo, hi - 1) if r not in equal])
+    change = rng.random((n_rows, n_cols)) < 0.05
+    change[ends, rng.integers(0, n_cols, size=ends.size)] = True
+    change[equal] = False
+    kind = np.where(change, rng.integers(0, 8, size=change.shape), -1)
+    ta, tb = MA.dtype.type, MB.dtype.type
+    up, down, flip = kind == 0, (kind == 1) | (kind == 2), kind == 3
+    MB[up], MB[down] = np.nextafter(MB[up], tb(np.inf)), np.nextafter(MB[down], tb(-np.inf))
+    MA[flip], MB[flip] = ta(0.0), tb(-0.0)
+    MB[(kind == 4) | (kind == 6)] = tb(np.nan)
+    MA[(kind == 5) | (kind == 6)] = ta(np.nan)
+    MB[kind == 7] = tb(np.inf)
+    # What a carried-over best would get wrong: the first row of turn t differs in ONE place, column 7 + t, by about
+    # 2^-(t + 1): less than the first row of the turn before it.  The row one turn before an equal row differs too.
+    # And NaN on one side and on both in the second row of every turn of more than two rows.
+    for t, (lo, hi) in enumerate(turns):
+        MA[lo], MB[lo] = cast(la, V[lo]), cast(lb, V[lo])
+        MB[lo, 7 + t] = cast(lb, V[lo, 7 + t] + 2.0 ** -(t + 1))
+        if hi - lo > 2:
+            MB[lo + 1, 3], MA[lo + 1, 4], MB[lo + 1, 4] = tb(np.nan), ta(np.nan), tb(np.nan)
+        if hi - 1 > lo:                                     # (the last row's change may have been a flipped zero: no difference)
+            MA[hi - 1, 9], MB[hi - 1, 9] = cast(la, V[hi - 1, 9]), np.nextafter(cast(lb, V[hi - 1, 9]), tb(np.inf))
+    for r in equal[equal >= TURN]:
+        MB[r - TURN, 2] = np.nextafter(cast(lb, V[r - TURN, 2]), tb(np.inf))
+    return MA, MB, equal, turns
+
+
+@pytest.mark.parametrize("n_rows", TALL)
+@pytest.mark.parametrize("la,lb", TALL_PAIRS)
+def test_more_rows_than_the_grid_has_waves(dev, la, lb, n_rows):
+    """8 197 x 40 and 24 577 x 40: the grid is capped at 2 048 workgroups, so a wave takes rows r, r + 8 192, ...: a row's
+    best, its place and its counts start afresh at every row, while a lane's zeros run on over all its rows."""
+    n_cols, floor = 40, 2.0 ** -20
+    MA, MB, equal, turns = tall_pair(la, lb, n_rows, n_cols, 90)
+    A, Bm = B.widen(la, MA), B.widen(lb, MB)
+    d = R.distance(A, Bm)
+    assert n_rows > TURN and len(turns) == -(-n_rows // TURN)
+    for lo, hi in turns:                                    # every turn holds rows that differ, NaN on one side and on both
+        assert (d[lo] > 0).any() and (d[hi - 1] > 0).any()
+        na, nb = np.isnan(A[lo:hi]), np.isnan(Bm[lo:hi])
+        assert hi - lo == 1 or ((na ^ nb).any() and (na & nb).any())
+    # a later row of a wave whose maximum is BELOW that of the wave's row one turn before: a best that is carried over shows
+    late = [lo for lo, _ in turns if lo] + equal[equal >= TURN].tolist()
+    assert len(late) >= len(turns) - 1 and all(d[r].max() < d[r - TURN].max() for r in late)
+    assert (d[TURN:].max(axis=1) < d[:n_rows - TURN].max(axis=1)).sum() >= len(late)
+    refs = {n_tol: R.sweep(A, Bm, TOLS[n_tol], floor) for n_tol in (8, 1)}
+    assert (refs[8][0][equal] == 0.0).all() and (refs[8][1][equal] == 0).all() and (refs[8][4][equal] == 0).all()
+    assert len(equal) >= len(turns) - 1 and refs[8][5][0] >= n_cols * len(equal) and refs[8][5].sum() == n_rows * n_cols
+    sa_, sb_ = B.SENTINEL[(la, "wide")], B.SENTINEL[(lb, "wide")]
+    va, vb = B.variants(la, n_rows, n_cols), B.variants(lb, n_rows, n_cols)
+    for i in range(max(len(va), len(vb))):
+        (tag_a, stride_a, base_a), (tag_b, stride_b, base_b) = va[i % len(va)], vb[i % len(vb)]
+        SA = dev.put(place(la, MA, stride_a, sa_).tobytes(), base_a)
+        SB = dev.put(place(lb, MB, stride_b, sb_).tobytes(), base_b)
+        for n_tol in (1, 8) if i == 0 else (8,):
+            what = (la, lb, n_rows, tag_a, tag_b, n_tol)
+            got = run_sweep(dev, SA, la, stride_a, SB, lb, stride_b, n_rows, n_cols, TOLS[n_tol], floor)
+            for g, w, name in zip(got, expected(refs[n_tol], n_rows, n_tol), NAMES):
+                same_bits(g, w, (what, name))
+        again = run_sweep(dev, SA, la, stride_a, SB, lb, stride_b, n_rows, n_cols, TOLS[8], floor)
+        for g, a in zip(got, again):
+            assert np.array_equal(B.bits(g), B.bits(a)), what
+        dev.release()
 
 
 # ---- 2. through the estimators -------------------------------------------------------------------------------------------

@@ -219,6 +219,37 @@ def test_many_small_pairs_in_one_call(dev):
     check_select(run.select(10), pieces, 10, "small pairs")
 
 
+def test_a_pair_longer_than_its_share_of_the_grid(dev):
+    """6000 pairs of 0 .. 40 x 0 .. 40, one of 70 x 60 and one of 3 x 300 in one call.  explain.hip caps the workgroups along y
+    at 16384 / n_pairs = 2: the 70 x 60 pair has five chunks of 1024 terms and the 3 x 300 pair five strips of 64 columns, so
+    the gather's chunk loop and the column sums' strip loop take a second and a third turn (with 3000 pairs the cap is 5 and
+    every loop runs once)."""
+    layout, n_rows, n_cols = B.ROWMAJOR_F32, 70, 129
+    _, stride, base = B.variants(layout, n_rows, n_cols)[0]
+    blk = B.make_block(layout, n_rows, n_cols, stride, 78, kind="dyadic")
+    rng = np.random.default_rng(9)
+    la = [rng.integers(0, n_rows, size=rng.integers(0, 41)) for _ in range(6000)]
+    lb = [rng.integers(0, n_cols, size=rng.integers(0, 41)) for _ in range(6000)]
+    la[1234:1234], lb[1234:1234] = [rng.integers(0, n_rows, size=70)], [rng.integers(0, n_cols, size=60)]
+    la.append(rng.integers(0, n_rows, size=3)), lb.append(rng.integers(0, n_cols, size=300))
+    n_pairs = len(la)
+    max_terms = max(len(a) * len(b) for a, b in zip(la, lb))
+    cap = 16384 // n_pairs                                                    # kBlocksWanted / n_pairs
+    assert n_pairs == 6002 and max_terms == 4200 and -(-max_terms // 1024) > cap >= 1
+    assert -(-max(len(b) for b in lb) // 64) > cap
+    case = Case(la, lb)
+    pieces = want_pieces(blk.A, case)
+    assert pieces[1234].shape == (70, 60) and pieces[-1].shape == (3, 300)
+    run = Run(dev, case)
+    same_bits(run.gather(dev.put(blk.raw, base), layout, stride, n_rows, n_cols), flat(pieces), "gather")
+    rs, cs, raw, cnt = run.reduce()
+    same_bits(rs, np.concatenate([p.sum(axis=1) + 0.0 for p in pieces]), "rows")               # (dyadic: exact in any order)
+    same_bits(cs, np.concatenate([p.sum(axis=0) + 0.0 for p in pieces]), "columns")
+    same_bits(raw, np.array([p.sum() + 0.0 for p in pieces]), "raw")
+    assert cnt.tolist() == [int(ER.contributors(p).sum()) for p in pieces]
+    check_select(run.select(10), pieces, 10, "a long pair among many")
+
+
 # ---- 2. planted values ------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", B.LAYOUTS)
 def test_a_planted_nan_poisons_its_row_its_column_and_raw(dev, layout):

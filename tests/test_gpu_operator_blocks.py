@@ -7,7 +7,9 @@ runs), so the device must give the bits of the NumPy product whatever its order 
 strides and bases of ``blocks.variants`` (a panel stride above the rows, a row-major stride that breaks 16-byte
 alignment, a base 4 / 8 bytes in), shapes on both sides of a strip, a tile and a panel, every column tile width and
 both sides of d = 8, where the matrix-vector forms end, both directions, NULL and permuted maps, three (alpha, beta) with
-powers of two, NaN in ``out`` where beta = 0, leading dimensions above d and a guard row.  To a bound: on the wide blocks with a normal X, within K 2^-52 sum |S| |X| of the
+powers of two, NaN in ``out`` where beta = 0, leading dimensions above d and a guard row; and, on the long blocks of
+``operator_ref.LONG_CASES`` (``blocks.make_long``), with two and three tiles of the contraction per workgroup in each of
+the three kernels, which no shape above reaches: there a part is one tile.  To a bound: on the wide blocks with a normal X, within K 2^-52 sum |S| |X| of the
 NumPy product, and the same bits twice."""
 import numpy as np
 import pytest
@@ -88,6 +90,40 @@ def test_apply_is_the_numpy_product_bit_for_bit(dev, layout, shape):
                             same_bits(got, want, what)
             dev.release()
             S = dev.put(blk.raw, base)
+        dev.release()
+
+
+@pytest.mark.parametrize("case", R.LONG_CASES, ids=R.LONG_IDS)
+@pytest.mark.parametrize("layout", B.LAYOUTS)
+def test_apply_over_several_tiles_per_part_bit_for_bit(dev, layout, case):
+    """The shapes of ``operator_ref.LONG_CASES``: a workgroup walks two or three tiles of the contraction, so the prefetch
+    of the next tile, the barriers between two tiles and a last part that is shorter than the others all run.  Same
+    protocol as above; the split is asked of the library, not trusted."""
+    lib = _operator.load()
+    R.assert_long_cases_walk_several_tiles(lib)
+    kernel, n_rows, n_cols, transpose, ds, _, _ = case
+    i = R.LONG_CASES.index(case)
+    rng = np.random.default_rng([layout, i, 14])
+    perms = (rng.permutation(n_rows).astype(np.int32), rng.permutation(n_cols).astype(np.int32))
+    n_out, n_in = (n_cols, n_rows) if transpose else (n_rows, n_cols)
+    X = R.exact_operand(rng, n_in, max(ds), layout)
+    for tag, stride, base in B.variants(layout, n_rows, n_cols):
+        blk = B.make_long(layout, n_rows, n_cols, stride, i)
+        S = dev.put(blk.raw, base)
+        for maps in ((None, None), perms):
+            E = effective(blk.A, maps[0], maps[1], transpose)
+            R.assert_exact(E, X)
+            P = E @ X
+            for d in ds:
+                tiles, parts, per, last = R.split_of(lib, case, d)
+                assert per >= 2, (case, d, tiles, parts)
+                for alpha, beta in SCALES[:2]:
+                    out0 = (np.full((n_out, d), np.nan) if beta == 0.0 else rng.integers(-64, 65, size=(n_out, d)) / 4.0)
+                    R.assert_exact(E, X[:, :d], alpha, beta, out0)
+                    want = alpha * P[:, :d] + (0.0 if beta == 0.0 else beta * out0)
+                    what = (layout, kernel, n_rows, n_cols, tag, transpose, maps[0] is None, d, alpha, beta, per, last)
+                    got = call_apply(dev, lib, S, blk, maps[0], maps[1], transpose, X, d, alpha, beta, out0, what)
+                    same_bits(got, want, what)
         dev.release()
 
 

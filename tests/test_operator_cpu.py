@@ -36,6 +36,15 @@ def test_sizes_and_bad_arguments_need_no_device():
     assert lib.simrank_operator_parts(70, 1100, 0, 3) == 5 and lib.simrank_operator_parts(70, 1100, 1, 8) == 2
     assert lib.simrank_operator_parts(32768, 32768, 0, 1) == 1 and lib.simrank_operator_parts(32768, 32768, 1, 1) == 47
     assert lib.simrank_operator_parts(1, 1, 0, 1) == 1 and lib.simrank_operator_parts(0, 0, 1, 64) == 1
+    # more than 64 tiles: a workgroup walks several (tests/operator_ref.LONG_CASES, what the GPU test runs).  In the
+    # table's order: (parts, tiles per part, tiles of the last part)
+    want = [(34, 2, 1), (34, 2, 1), (44, 3, 3), (34, 2, 1), (44, 3, 3), (33, 2, 2), (43, 3, 3), (33, 2, 1), (33, 2, 2), (44, 3, 1)]
+    tiles = [67, 67, 132, 67, 132, 66, 129, 65, 66, 130]
+    assert len(want) == len(R.LONG_CASES)
+    for case, w, n_tiles in zip(R.LONG_CASES, want, tiles):
+        for d in case[4]:
+            assert R.split_of(lib, case, d) == (n_tiles,) + w, (case, d)
+    R.assert_long_cases_walk_several_tiles(lib)
     assert lib.simrank_operator_parts(-1, 5, 0, 1) == -1 and lib.simrank_operator_parts(5, 5, 2, 1) == -1
     assert lib.simrank_operator_parts(5, 5, 0, 0) == -1 and lib.simrank_operator_parts(5, 5, 0, 65) == -1
     assert re.search(r"#define SIMRANK_OPERATOR_NARROW 8\b", A.header(_operator))
