@@ -66,36 +66,44 @@ def check_diversity(diversity, top_k):
 
 
 # ---- the device half -------------------------------------------------------------------------------------------------
-def run(reader, ptr, ids, w, k, excl, d, timing=None):
+def run(reader, ptr, ids, w, k, excl, d, timing=None, among=None):
     """The baskets (``ptr``, ``ids``, ``w``, ``excl`` as ``_sets.run`` takes them) scored on ``reader``'s iterate, one
     block holding every row and column (``_query.Reader``; a solver's ``one_block`` scope), or the
     ``_neighbors.NeighborReader`` of a pruned model, and of each the ``k`` picks at diversity ``d`` -> (ids int32
     [n_sets, k]: caller ids, -1 past the last pick; score, penalty, value float64 [n_sets, k]: zeros there).  Per band of
     ``_sets.run``: the score kernel, then one pick kernel on the band where it lies; ``reader.inv`` tells the block row of
-    a candidate, the block's column map its column.  ``timing`` also receives ``pick_ms``."""
+    a candidate, the block's column map its column.  ``timing`` also receives ``pick_ms``.  ``among``: the caller ids
+    (int32, sorted, each once) of the only candidates, as ``_sets.run`` takes them: the band then has one column per
+    candidate, in id order, candidate b's row and column are those of node ``among[b]``, and the picks come back as band
+    columns and are mapped to caller ids on the host (a pruned model's band keeps every column, the others marked)."""
     from . import _sets
     lib, ops, n = load(), reader.ops, reader.n
     n_sets = int(ptr.size - 1)
-    k = int(min(k, max(1, n)))
+    tables = reader._tables() if hasattr(reader, "score_band") else None
+    if among is not None:
+        among = np.ascontiguousarray(among, dtype=np.int32)
+    narrowed = among is not None and tables is None        # the band holds the candidates' columns only
+    nc = int(among.size) if narrowed else n                # columns of the band
+    k = int(min(k, max(1, nc if among is None else among.size)))
     d = float(d)
     rel_w = 1.0 - d
     idx = np.full((n_sets, k), -1, dtype=np.int32)
     score, pen, val = (np.zeros((n_sets, k), dtype=np.float64) for _ in range(3))
-    if n_sets == 0 or n == 0:
+    if n_sets == 0 or nc == 0 or (among is not None and among.size == 0):
         return idx, score, pen, val
     (b,) = reader.blocks
     assert b["cols"] == n and b.get("col_lo", 0) == 0
-    tables = reader._tables() if hasattr(reader, "score_band") else None
     with Scratch(ops) as scratch:
-        row_pos = None if tables is not None else scratch.put(reader.inv)
+        row_pos = None if tables is not None else scratch.put(reader.inv[among] if narrowed else reader.inv)
+        col_pos = row_pos if narrowed else None if tables is not None else reader._col_map(0)[0]
         held = {}
 
         def consume(q0, m, pieces, stage):
             ((_, band, cols, _),) = pieces
             if not held:                                     # (the first band is the largest)
-                held.update(m=m, work=scratch.malloc(lib.simrank_diverse_workspace_bytes(m, n)),
+                held.update(m=m, work=scratch.malloc(lib.simrank_diverse_workspace_bytes(m, nc)),
                             idx=scratch.malloc(4 * m * k), **{x: scratch.malloc(8 * m * k) for x in ("score", "pen", "val")})
-            assert m <= held["m"] <= MAX_BLOCKS and cols == n
+            assert m <= held["m"] <= MAX_BLOCKS and cols == nc
             outs = (held["idx"], held["score"], held["pen"], held["val"])
             if tables is not None:
                 stage("pick_ms", lambda: check(lib.simrank_diverse_pick_lists(
@@ -103,11 +111,13 @@ def run(reader, ptr, ids, w, k, excl, d, timing=None):
                     ops.stream), "simrank_diverse_pick_lists"))
             else:
                 stage("pick_ms", lambda: check(lib.simrank_diverse_pick(
-                    b["ptr"], b["layout"], b["stride"], b["rows"], n, row_pos, reader._col_map(0)[0], n, band, n, m, k,
+                    b["ptr"], b["layout"], b["stride"], b["rows"], n, row_pos, col_pos, nc, band, nc, m, k,
                     rel_w, d, *outs, held["work"], ops.stream), "simrank_diverse_pick"))
             for host, dev in zip((idx, score, pen, val), outs):
                 ops.d2h(host[q0:q0 + m], dev, host.itemsize * m * k)
             ops.synchronize()                                # (the next band's picks overwrite the four outputs)
 
-        _sets.run(reader, ptr, ids, w, None, excl, timing, consumer=consume)
+        _sets.run(reader, ptr, ids, w, None, excl, timing, consumer=consume, among=among)
+    if narrowed:
+        idx[idx >= 0] = among[idx[idx >= 0]]
     return idx, score, pen, val

@@ -165,15 +165,37 @@ class _KeptModel:
         _, ib = self._ids(j, labels, b)
         return solver.pair_values(j, ia, ib)
 
-    def most_similar(self, nodes, k, group=None):
+    def most_similar(self, nodes, k, group=None, among=None, exclude=None):
         """Long frame (node, rank, neighbor, similarity): the rows of the ``fit(top_k=k)`` frame of the nodes in ``nodes``,
-        blocks in the order of ``nodes``."""
+        blocks in the order of ``nodes``.
+
+        ``among`` / ``exclude``: None, or a non-string iterable of fitted labels of the group, shared by all queries
+        (duplicates collapse, the order does not matter, empty is allowed; a str, bytes or a scalar is a ValueError, an
+        unknown label a KeyError).  The candidates of node a are then ``(among or every node) - exclude - {a}``, ranked
+        in the same order (similarity descending, label position ascending; NaN never listed); a node with fewer than
+        k candidates gets fewer rows, an empty candidate set a frame of zero rows.  ``k`` is clamped to ``max(1, |among -
+        exclude|)`` and may then be at most 4096 (ValueError); every refusal comes before any device work.  The
+        selection reads the candidates' elements in place on the device, once per query (libsimrank_candidates.so), per
+        column block with a merge on the host under ``LocalWorld(P)``; a pruned model is answered on the host for its
+        matrix P: a candidate counts with its listed value, or with the +0.0 of an absent entry.  With both None the
+        call is what it was without the keywords.  ``fold_in(top_k=)``, ``rank_sets``, ``rank_recommended``,
+        ``evaluate``, ``top_k()`` and ``pairs()`` take no candidate filter, and a ``TorchWorld`` model answers none."""
+        from . import _candidates
         from ._query import check_k
         k = check_k(k)
         solver, j, labels = self._kept(group)
+        lab, _ = self._ids(j, labels, [])
+        cand = _candidates.prepare(among, exclude, lab)
+        if cand is None:
+            self._check_kept_neighbors(solver, [j], k)
+            lab, ids = self._ids(j, labels, nodes)
+            return _long_frame("node", "similarity", lab.take(ids), lab, *solver.topk_of(j, ids, k))
+        k = _candidates.clamp_k(k, cand.size)
         self._check_kept_neighbors(solver, [j], k)
+        if not hasattr(solver, "topk_among"):
+            raise ValueError("among= / exclude= need a solver behind the C ABI (fit on one GPU or LocalWorld(P))")
         lab, ids = self._ids(j, labels, nodes)
-        return _long_frame("node", "similarity", lab.take(ids), lab, *solver.topk_of(j, ids, k))
+        return _long_frame("node", "similarity", lab.take(ids), lab, *solver.topk_among(j, ids, cand, k))
 
     def fold_in(self, neighbors, weights=None, prior=None, names=None, group=None, top_k=None):
         """Similarities of nodes that were NOT in the fitted graph: for each new node, the row the NEXT update would
@@ -211,7 +233,8 @@ class _KeptModel:
             return pd.DataFrame(solver.fold_in(j, lists, w, prior), index=new_index, columns=out_index.copy())
         return _long_frame("node", "similarity", new_index, out_index, *solver.fold_in(j, lists, w, prior, top_k=k))
 
-    def score_sets(self, sets, weights=None, names=None, group=None, top_k=None, exclude="members", diversity=None):
+    def score_sets(self, sets, weights=None, names=None, group=None, top_k=None, exclude="members", diversity=None,
+                   among=None):
         """Basket queries: for each basket (a sequence of labels of FITTED nodes of ``group``, repeats counting as often
         as they occur) the row
 
@@ -232,19 +255,37 @@ class _KeptModel:
         the picks p made so far (row p of the group's matrix; +0.0 before the first pick and never below it), and the
         next pick is the candidate with the greatest ``value = ((1 - d) * score) - (d * penalty)``, three float64
         operations, ties by label position.  -> the long frame (set, rank, neighbor, score, penalty, value), ``rank`` the
-        order of picking.  ``d = 0`` picks what ``top_k`` alone does."""
+        order of picking.  ``d = 0`` picks what ``top_k`` alone does.
+
+        ``among`` (with ``top_k``; as ``most_similar`` takes it: None or a non-string iterable of fitted labels of the
+        group, shared by all baskets): the candidates of a basket are ``among`` minus its exclusions, with or without
+        ``diversity``.  Only the candidates' columns are scored, so the band on the device is |among| wide; a score
+        depends on its own column alone and keeps its bits.  ``among`` without ``top_k`` is a ValueError."""
         from . import _diverse, _sets
         solver, j, labels = self._kept(group)
         d = _diverse.check_diversity(diversity, top_k)
         index, _ = self._ids(j, labels, [])
+        cand = self._among(among, top_k, index)
         ptr, ids, w, names, k, excl = _sets.prepare(sets, index, weights=weights, names=names, top_k=top_k,
                                                     exclude=exclude)
         who = pd.RangeIndex(ptr.size - 1) if names is None else pd.Index(names)
+        more = {} if cand is None else {"among": cand}
         if d is not None:
-            return _diverse_frame("set", who, index, *solver.score_diverse(j, ptr, ids, w, k, excl, d))
+            return _diverse_frame("set", who, index, *solver.score_diverse(j, ptr, ids, w, k, excl, d, **more))
         if k is None:
             return pd.DataFrame(solver.score_sets(j, ptr, ids, w), index=who, columns=index.copy())
-        return _long_frame("set", "score", who, index, *solver.score_sets(j, ptr, ids, w, k, excl))
+        return _long_frame("set", "score", who, index, *solver.score_sets(j, ptr, ids, w, k, excl, **more))
+
+    @staticmethod
+    def _among(among, top_k, index):
+        """``among=`` of the band queries, checked before any device work: None, or the sorted caller ids of the
+        candidates (``_candidates.prepare``); ValueError without ``top_k``."""
+        from . import _candidates
+        if among is None:
+            return None
+        if top_k is None:
+            raise ValueError("among narrows a selection: give top_k as well")
+        return _candidates.prepare(among, None, index)
 
     def matmul(self, X, transpose=False, group=None):
         """The model as a linear operator: ``S @ X`` of the group's matrix (``transpose=True``: ``S.T @ X``; the matrices
@@ -303,7 +344,7 @@ class _KeptModel:
         return (pd.DataFrame(V, index=index.copy(), columns=cols),
                 pd.Series(w, index=cols.copy(), name="eigenvalue", dtype=np.float64))
 
-    def recommend(self, nodes, k, group=None, exclude_seen=True, diversity=None):
+    def recommend(self, nodes, k, group=None, exclude_seen=True, diversity=None, among=None):
         """Leg 1 of the update for chosen rows: for each fitted node u of ``group`` the k best of ``(W . S)[u, :]``, the
         scores of u's neighbours' rows (its in-neighbours for the directed classes; for the bipartite classes the
         group-2 neighbours of a group-1 node, read from group 2's matrix, and the other way round), every weight
@@ -313,20 +354,24 @@ class _KeptModel:
         -> long frame (node, rank, neighbor, score), blocks in the order of ``nodes``; ``neighbor`` is a node of the
         group the basket lives in.  A node without neighbours gets no rows.  ``diversity=d``: the k picked by maximal
         marginal relevance as ``score_sets(diversity=d)`` picks them, the penalties read from the matrix the baskets live
-        in -> (node, rank, neighbor, score, penalty, value)."""
+        in -> (node, rank, neighbor, score, penalty, value).  ``among``: as ``score_sets`` takes it, labels of the group
+        the ``neighbor`` column lives in; the candidates of a node are ``among`` minus what ``exclude_seen`` removes."""
         from . import _diverse, _sets
         solver, side, j, index, src_j, src_index = self._across(group)
         if not isinstance(exclude_seen, bool):
             raise ValueError(f"exclude_seen must be True or False, not {exclude_seen!r}")
         d = _diverse.check_diversity(diversity, k)
         k = _sets.check_top_k(k, len(src_index))
+        cand = self._among(among, k, src_index)
+        more = {} if cand is None else {"among": cand}
         _, ids = self._ids(j, index, nodes)
         spec = solver.specs[side]
         ptr, members, w, excl = _sets.csr_baskets(spec.csr, spec.rowscale, ids, src_j == j, exclude_seen)
         if d is not None:
             return _diverse_frame("node", index.take(ids), src_index,
-                                  *solver.score_diverse(src_j, ptr, members, w, k, excl, d), keep_rows=np.diff(ptr) > 0)
-        idx, val = solver.score_sets(src_j, ptr, members, w, k, excl)
+                                  *solver.score_diverse(src_j, ptr, members, w, k, excl, d, **more),
+                                  keep_rows=np.diff(ptr) > 0)
+        idx, val = solver.score_sets(src_j, ptr, members, w, k, excl, **more)
         return _long_frame("node", "score", index.take(ids), src_index, idx, val, keep_rows=np.diff(ptr) > 0)
 
     def explain(self, a, b, k=10, group=None, max_terms=2 ** 27):

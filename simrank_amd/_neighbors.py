@@ -261,6 +261,12 @@ class NeighborSolver(SolverQueries):
     def topk_of(self, j, node_ids, k):
         return self._reader(j).topk_of(node_ids, clamp_k(k, self.n[j]))
 
+    def topk_among(self, j, node_ids, cand_ids, k):
+        """``SolverQueries.topk_among`` for the matrix P, on the host after one copy of the tables: a candidate counts
+        with its listed value, or with the +0.0 of an absent entry."""
+        from . import _candidates
+        return _candidates.topk_of_lists(self.lists(j), node_ids, cand_ids, k)
+
     def result(self, j=0):
         return self.rows(j, np.arange(self.n[j], dtype=np.int32))
 
@@ -274,11 +280,11 @@ class NeighborSolver(SolverQueries):
         self._reader(j)                                      # (raises when the tables were released)
         return self.tables[j].host()
 
-    def score_diverse(self, j, ptr, ids, w, k, excl, d, timing=None):
+    def score_diverse(self, j, ptr, ids, w, k, excl, d, timing=None, among=None):
         """``SolverQueries.score_diverse`` for the matrix P, on the device: the band from ``score_band``, the picks from
         ``simrank_diverse_pick_lists`` on the tables."""
         from . import _diverse
-        return _diverse.run(self._reader(j), ptr, ids, w, k, excl, d, timing)
+        return _diverse.run(self._reader(j), ptr, ids, w, k, excl, d, timing, among=among)
 
     def pairs(self, j, t, max_pairs):
         """Side j's kept off-diagonal entries at least ``t``: (offsets [n + 1], neighbour ids ascending within a node,

@@ -131,6 +131,13 @@ class SolverQueries:
         the solver's ``topk`` clamps it."""
         return self._reader(j).topk_of(node_ids, clamp_k(self.n[j], k))
 
+    def topk_among(self, j, node_ids, cand_ids, k):
+        """(ids int32 [len(node_ids), k], values float64): of those nodes the k best among the candidates ``cand_ids``
+        (caller ids, int32, sorted, each once) other than the node itself (``_candidates.topk_of``); ``k`` as the caller
+        clamped it to the candidates."""
+        from . import _candidates
+        return _candidates.topk_of(self._reader(j), node_ids, cand_ids, k)
+
     def fold_in(self, j, lists, w, prior=None, top_k=None, timing=None):
         """Rows of NEW nodes joining side j (``_foldin.Folder.run``): ``lists`` hold ids of the side the update reads
         (the same side for the one-matrix classes, the other one for the bipartite classes).  Side j's CSR goes to the
@@ -148,11 +155,12 @@ class SolverQueries:
             self._folders[j] = _foldin.Folder(self._reader(src), spec.csr, spec.rowscale, spec.coef, spec.lbd, evidence)
         return self._folders[j].run(lists, w, prior, top_k, timing)
 
-    def score_sets(self, j, ptr, ids, w, k=None, excl=None, timing=None):
+    def score_sets(self, j, ptr, ids, w, k=None, excl=None, timing=None, among=None):
         """Basket scores on side j's iterate (``_sets.run``): ``ptr`` / ``ids`` / ``w`` the baskets as offsets, node ids
-        of side j and weights; the dense rows, or with ``k`` the k best per basket outside ``excl``."""
+        of side j and weights; the dense rows, or with ``k`` the k best per basket outside ``excl`` (and, with ``among``,
+        among those sorted caller ids only)."""
         from . import _sets
-        return _sets.run(self._reader(j), ptr, ids, w, k, excl, timing)
+        return _sets.run(self._reader(j), ptr, ids, w, k, excl, timing, among=among)
 
     def score_ranks(self, j, ptr, ids, w, excl, tptr, tids, timing=None):
         """Held-out ranks on side j's iterate (``_rank.run``): the baskets as ``score_sets`` takes them, ``tptr`` /
@@ -161,13 +169,13 @@ class SolverQueries:
         from . import _rank
         return _rank.run(self._reader(j), ptr, ids, w, excl, tptr, tids, timing)
 
-    def score_diverse(self, j, ptr, ids, w, k, excl, d, timing=None):
+    def score_diverse(self, j, ptr, ids, w, k, excl, d, timing=None, among=None):
         """The k picks per basket at diversity ``d`` on side j's iterate (``_diverse.run``): the baskets as ``score_sets``
         takes them -> (ids int32, score, penalty, value float64), each [n_sets, k]; the score band stays on the device.
         A side held in several column blocks is first packed into one (``one_block``)."""
         from . import _diverse
         with self.one_block(j) as reader:
-            return _diverse.run(reader, ptr, ids, w, k, excl, d, timing)
+            return _diverse.run(reader, ptr, ids, w, k, excl, d, timing, among=among)
 
     def apply_operator(self, j, X, transpose=False, timing=None):
         """Side j's matrix as a linear operator (``_operator.product``): ``S @ X``, or ``S.T @ X``, for the host float64

@@ -131,7 +131,17 @@ def _block_exclusions(excl, ids_sorted, whole):
     return out, np.ascontiguousarray(at[hit], dtype=np.int32)
 
 
-def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, consumer=None):
+def _outside(excl, among, n, n_sets):
+    """``excl`` (or None) with every caller id outside ``among`` added to every basket: what marks the band of a reader
+    that writes all n columns (a pruned model's ``score_band``) so that only the candidates remain."""
+    rest = np.setdiff1d(np.arange(n, dtype=np.int32), among, assume_unique=True).astype(np.int32)
+    if excl is None:
+        return np.arange(n_sets + 1, dtype=np.int64) * rest.size, np.tile(rest, n_sets)
+    ptr, ids = excl
+    return join([np.concatenate([ids[ptr[q]:ptr[q + 1]], rest]) for q in range(n_sets)])
+
+
+def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, consumer=None, among=None):
     """Score the baskets (``ptr`` int64 [n_sets + 1], ``ids`` int32 caller ids, ``w`` float64) on ``reader``'s iterate
     (``_query.Reader``, or the ``_neighbors.NeighborReader`` of a pruned model, whose ``score_band`` fills the band from
     the neighbour lists instead) -> float64 [n_sets, n] in the caller's column order, or with ``k`` (ids int32 [n_sets, k], values
@@ -144,12 +154,24 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
     reader's stream is done before the next band overwrites the slab (``_rank.run``).  One band of baskets holds at most
     ``_query.SLAB_BYTES`` on the device; per band one score kernel per column block, then one copy of the band or one
     selection per block with the pieces merged on the host.  ``timing``: a dict that receives the milliseconds of the
-    stages (HIP events; serialises them)."""
+    stages (HIP events; serialises them).  ``among`` (with ``k`` or a ``consumer``): the caller ids (int32, sorted, each
+    once) of the only candidates.  A block then scores its candidates' columns alone: ``col_pos`` their positions, ``n_out``
+    their number, so the band is |among| wide and a piece's columns are the block's candidates in id order (a consumer
+    always gets their device ids); a score depends on its own column only and keeps its bits.  A pruned model's
+    ``score_band`` writes every column: there the columns outside ``among`` are marked as ``excl`` marks them."""
     from . import _query, hostpool
     lib, ops, n = load(), reader.ops, reader.n
     order = GRID_ORDER if grid_order is None else int(grid_order)
     n_sets = int(ptr.size - 1)
     marked = k is not None or consumer is not None         # the band carries the exclusions and the blocks their ids
+    score_band = getattr(reader, "score_band", None)
+    if among is not None:
+        if not marked:
+            raise ValueError("among narrows a selection: give k or a consumer")
+        among = np.ascontiguousarray(among, dtype=np.int32)
+        if score_band is not None:                           # (every column is written: mark, do not narrow)
+            excl, among = (_outside(excl, among, n, n_sets) if n_sets and n else excl), None
+    width = n if among is None else int(among.size)        # columns of the band
     if consumer is not None:
         if k is not None:
             raise ValueError("a consumer takes the band instead of a selection: k must be None")
@@ -157,26 +179,31 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
     elif k is None:
         result = hostpool.empty_f64(n_sets, n)
     else:
-        k = int(min(k, max(1, n)))
+        k = int(min(k, max(1, width)))
         result = (np.full((n_sets, k), -1, dtype=np.int32), np.zeros((n_sets, k), dtype=np.float64))
-    if n_sets == 0 or n == 0:
+    if n_sets == 0 or width == 0:
         return result
     # a band's workgroups on one block, in either grid order: at most band * max(8, chunks + 7)
     per_basket = max(8, -(-max(b["cols"] for b in reader.blocks) // CHUNK) + 7)
-    walk = bands(n_sets, 8 * n, MAX_BLOCKS // per_basket)
-    whole = len(reader.blocks) == 1
-    score_band = getattr(reader, "score_band", None)
+    walk = bands(n_sets, 8 * width, MAX_BLOCKS // per_basket)
+    whole = len(reader.blocks) == 1 and among is None
     stage = functools.partial(_driver.stage, ops, timing)
     with Scratch(ops) as scratch:
-        slab, put = scratch.malloc(8 * walk.size * n), scratch.put
+        slab, put = scratch.malloc(8 * walk.size * width), scratch.put
         ptr_dev = put(ptr.astype(np.int64, copy=False))
         pos_dev = put(reader.inv[ids]) if ids.size else None
         w_dev = put(np.asarray(w, dtype=np.float64)) if ids.size else None
         per_block = []
         for i, b in enumerate(reader.blocks):
-            cmap, ids_sorted = reader._col_map(i)
+            if among is None:
+                cmap, ids_sorted = reader._col_map(i)
+            else:                                            # (the block's candidates, in id order, and where they lie)
+                at = reader.inv[among].astype(np.int64) - b.get("col_lo", 0)
+                mine = (at >= 0) & (at < b["cols"])
+                ids_sorted = np.ascontiguousarray(among[mine])
+                cmap = put(at[mine].astype(np.int32)) if ids_sorted.size else None
             xp = xc = cid = None
-            if marked:
+            if marked and ids_sorted.size:
                 if excl is not None:
                     bp, bc = _block_exclusions(excl, ids_sorted, whole)
                     xp, xc = put(bp), put(bc if bc.size else np.zeros(1, dtype=np.int32))
@@ -184,14 +211,14 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
                     cid = put(np.ascontiguousarray(ids_sorted, dtype=np.int32))
             per_block.append((b, cmap, ids_sorted, xp, xc, cid))
         if k is not None:
-            kks = [int(min(k, b["cols"])) for b in reader.blocks]
+            kks = [int(min(k, p[2].size)) for p in per_block]
             idx_dev = [scratch.malloc(4 * walk.size * max(1, kk)) for kk in kks]
             val_dev = [scratch.malloc(8 * walk.size * max(1, kk)) for kk in kks]
         stitch = None if whole or marked else np.empty((walk.size, n), dtype=np.float64)
         for q0, m in walk:
             off, pieces = 0, []
             for i, (b, cmap, ids_sorted, xp, xc, cid) in enumerate(per_block):
-                cols = b["cols"]
+                cols = int(ids_sorted.size)                  # (output columns; without among the block's own)
                 if not cols:
                     continue
                 piece = slab + 8 * off
@@ -200,8 +227,9 @@ def run(reader, ptr, ids, w, k=None, excl=None, timing=None, grid_order=None, co
                                                          None if xp is None else xp + 8 * q0, xc, piece, cols))
                 else:
                     stage("score_ms", lambda: check(lib.simrank_sets_score(
-                        b["ptr"], b["layout"], b["stride"], b["rows"], cols, cmap, cols, ptr_dev + 8 * q0, pos_dev, w_dev, m,
-                        None if xp is None else xp + 8 * q0, xc, piece, cols, order, ops.stream), "simrank_sets_score"))
+                        b["ptr"], b["layout"], b["stride"], b["rows"], b["cols"], cmap, cols, ptr_dev + 8 * q0, pos_dev,
+                        w_dev, m, None if xp is None else xp + 8 * q0, xc, piece, cols, order, ops.stream),
+                        "simrank_sets_score"))
                 if k is not None:
                     kk = kks[i]
                     stage("topk_ms", lambda: check(lib.simrank_sets_topk(
