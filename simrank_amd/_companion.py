@@ -1,6 +1,6 @@
-"""What the ctypes bindings of the twenty companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
+"""What the ctypes bindings of the twenty-one companion libraries (``_select``, ``_f64``, ``_query``, ``_foldin``, ``_model``,
 ``_sets``, ``_neighbors``, ``_profile``, ``_cluster``, ``_rank``, ``_linkage``, ``_groups``, ``_kmedoids``, ``_explain``,
-``_compare``, ``_diverse``, ``_operator``, ``_density``, ``_hdbscan``, ``_candidates``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
+``_compare``, ``_diverse``, ``_operator``, ``_density``, ``_hdbscan``, ``_candidates``, ``_exemplars``) share: where libsimrank_NAME.so and include/simrank_NAME.h lie,
 the lazy load with the version check, ``check``, and the layout codes of a block of an iterate.  A binding keeps its
 prototypes, structures and host helpers.  The rest of what the bindings share lives elsewhere: the device scratch, the
 timed stage and the band walk in ``_driver``, the scalar argument checks in ``_checks``, and the two decisions of every "a

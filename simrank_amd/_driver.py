@@ -1,5 +1,5 @@
 """What the companion drivers (``_query``, ``_sets``, ``_rank``, ``_foldin``, ``_neighbors``, ``_profile``, ``_cluster``,
-``_linkage``, ``_groups``, ``_kmedoids``, ``_explain``, ``_compare``, ``_diverse``, ``_density``, ``_model``) share on the host: the lifetime of a call's device scratch, the timed stage, the band walk, the stitch of
+``_linkage``, ``_groups``, ``_kmedoids``, ``_explain``, ``_compare``, ``_diverse``, ``_density``, ``_model``, ``_exemplars``) share on the host: the lifetime of a call's device scratch, the timed stage, the band walk, the stitch of
 column blocks and the label lists.  ``ops`` is the engine's ``HipOps`` (or a double with its methods); nothing here
 calls a library.
 """

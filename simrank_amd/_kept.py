@@ -914,6 +914,66 @@ class _KeptModel:
                                                "changed": np.array(changed, dtype=np.int64),
                                                "objective": np.array(objective, dtype=np.float64)})
 
+    def exemplars(self, k, given=None, lazy=True, group=None):
+        """Which k nodes stand for all the fitted nodes: greedy facility location.  k times, the node is picked whose row
+        raises ``sum over the nodes a of max over the picked m of S[m, a]`` the most; the objective is submodular, so the
+        picks are within ``1 - 1/e`` of the best set.  ``picks["exemplar"]`` seeds ``kmedoids``.  ``group=1 | 2`` for the
+        bipartite classes.
+
+        Elements.  ``v(m, a) = S[m, a]``: row m, the element ``similarity(m, a)`` reads, widened as ``rows`` widens it
+        and then to float64.  This is the orientation of ``assign``: a medoid's ROW covers the nodes.  Every column
+        counts, m's own stored diagonal element included.
+
+        Cover.  ``cover[a]`` starts at +0.0: a node nothing stands for is covered at similarity 0.  Applying row p sets
+        ``cover[a] = v(p, a)`` iff ``v(p, a) > cover[a]``; that is false for a NaN, which never covers, never counts and
+        never gains.  ``given``: None or a sequence of distinct fitted labels; their rows are applied first, in the order
+        given, and they are never picked.
+
+        Gain.  ``term(m, a) = v(m, a) - cover[a]`` if ``v(m, a) > cover[a]``, else +0.0: one float64 subtraction, nothing
+        fused.  ``gain(m)`` is the float64 sum of the terms over all columns, in an order that depends on the number of
+        columns alone and is the same for every storage (include/simrank_exemplars.h states it): no floating-point
+        atomics, two runs give the same bits, and ``|gain - exact| <= (N + 1) * 2^-52 * (the exact sum of the terms)``.
+
+        Picks.  k times the candidate (a node neither picked nor given) that is first in the order (gain descending,
+        position in the dense frame's label order ascending) is picked and its row applied.  ``1 <= k <= N - len(given)``.
+
+        Monotonicity.  ``cover`` only rises; rounded subtraction is monotone and so is rounded addition in a fixed tree,
+        so a gain computed against an older cover is an upper bound of the gain now, in floating point as in exact
+        arithmetic.  ``lazy=True`` relies on it: it keeps every candidate's last gain as a bound, refreshes the first
+        ``_exemplars.BATCH`` stale candidates in the order above until the first candidate is fresh, and returns the bits
+        ``lazy=False`` (one sweep of all rows per pick) returns; only ``evaluated`` differs.  ``lazy=True`` is the
+        default because it is the faster one (DESIGN.md 4.33 has the numbers).
+
+        -> ``(picks, coverage)``.  ``picks``: one row per pick, index ``rank`` 0 .. k - 1, columns ``exemplar`` (the
+        label), ``gain`` (float64: the fresh gain at the moment of the pick), ``raised`` (int64: the columns whose cover
+        the pick raised, exact) and ``evaluated`` (int64: the rows whose gain was computed for this pick; with
+        ``lazy=False`` the number of candidates).  ``coverage``: a float64 Series named ``"coverage"`` over the dense
+        frame's labels in its order, the final ``cover``: maxima only, so every bit equals ``np.maximum.reduce`` over
+        ``rows(given + picked)`` with the +0.0 start and the NaN rule.
+
+        A bad ``k`` (not an int, a bool, below 1, above ``N - len(given)``), a bad ``given`` (a str, a scalar, a
+        repeated label), a bad ``lazy`` (no bool) or ``group`` is a ValueError, an unknown label in ``given`` a KeyError,
+        all before any device work.
+
+        The rows are read in place on the device (libsimrank_exemplars.so); per round a list of rows goes up and their
+        gains come down.  Where ``kmedoids`` runs: kept, compact and loaded models, f32, fp16-held and float64.  A model
+        held in several column blocks (``LocalWorld(P)``) is packed into one temporary block once per call.  A pruned
+        model is answered on the host for its matrix P: absent entries are +0.0 and never gain, and a gain there is
+        ``math.fsum`` of the terms.  The sum runs over the columns as the model holds them, so on a model that still
+        holds its plan (the solver's order) a gain may differ in its last bits from the compact model's, and two
+        candidates tied to within the rounding bound may then swap; compact and loaded models (the frame's order) are
+        the canonical form.  The model is left unchanged."""
+        from . import _exemplars
+        solver, j, lab = self._kept(group)
+        index, _ = self._ids(j, lab, [])
+        at = _exemplars.check_given(given, index)
+        k = _exemplars.check_k(k, len(index), at.size)
+        lazy = _exemplars.check_lazy(lazy)
+        picked, gain, raised, evaluated, cover = _exemplars.exemplars(solver, j, k, at, lazy)
+        picks = pd.DataFrame({"exemplar": index.take(picked).to_numpy(), "gain": gain, "raised": raised,
+                              "evaluated": evaluated}, index=pd.RangeIndex(k, name="rank"))
+        return picks, pd.Series(cover, index=index.copy(), name="coverage")
+
     def compare(self, other, tolerances=(1e-5,), top_k=10, floor=0.0):
         """How far apart two models of one graph are: ``other`` is another estimator holding a model (kept, compact or
         loaded; any mix of f32, fp16-held and float64; ``other is self`` is allowed and gives all zeros).  Both models

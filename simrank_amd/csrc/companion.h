@@ -1,10 +1,10 @@
-// What the companion libraries share, and nothing of the main library.  All twenty (select, f64, query, foldin, model, sets,
-// neighbors, profile, cluster, rank, linkage, groups, kmedoids, explain, compare, diverse, operator, density, hdbscan, candidates) take the error plumbing of a C entry point; all but f64 and rank (which reads a
+// What the companion libraries share, and nothing of the main library.  All twenty-one (select, f64, query, foldin, model, sets,
+// neighbors, profile, cluster, rank, linkage, groups, kmedoids, explain, compare, diverse, operator, density, hdbscan, candidates, exemplars) take the error plumbing of a C entry point; all but f64 and rank (which reads a
 // float64 score band, not an iterate) take the layouts a block of an iterate is read in, and what depends on them:
 //     one element      Stored<L>, offset_of<L>, load<L>, elem<L>: query, sets, neighbors, model, groups, kmedoids, explain,
-//                      compare, diverse, operator, density, hdbscan, candidates
-//     host checks      check_block: query, sets, neighbors, model, groups, kmedoids, explain, compare, diverse, operator, candidates;
-//                      plan_launch: select, profile, cluster, linkage, density, hdbscan;  quad_vector_loads: sets, kmedoids, compare, diverse, operator
+//                      compare, diverse, operator, density, hdbscan, candidates, exemplars
+//     host checks      check_block: query, sets, neighbors, model, groups, kmedoids, explain, compare, diverse, operator, candidates, exemplars;
+//                      plan_launch: select, profile, cluster, linkage, density, hdbscan;  quad_vector_loads: sets, kmedoids, compare, diverse, operator, exemplars
 //     layout dispatch  with_layout, a runtime layout code as a template argument: all but model's pair dispatch
 //     the 16-byte walk Elem<L>, WALK_GEOMETRY and WALK_LOAD, the lane geometry and the load phase of a sweep: select,
 //                      profile, cluster, linkage, density, hdbscan
