@@ -1,11 +1,14 @@
 """tests/far.py without a device: the far geometries reach the offsets their table states, the scatter plan stays inside
 the arena and does not overlap, the filler beats every value of every block, and at a small stride the plan applied to a
-filler-filled host buffer is ``blocks.encode`` wherever the plan wrote."""
+filler-filled host buffer is ``blocks.encode`` wherever the plan wrote.  And the inputs of the exemplars and candidates
+far tests (tests/far_cases.py) are sensitive: evaluated on the matrix a narrowed address would read, their references
+give other gains, another cover and other top-k ids."""
 import numpy as np
 import pytest
 
 from tests import blocks as B
 from tests import far as F
+from tests import far_cases as FC
 
 KINDS = ("dyadic", "wide")
 P31, P32 = 1 << 31, 1 << 32
@@ -115,3 +118,50 @@ def test_the_plan_reproduces_encode_at_a_small_stride(layout, kind):
             (B.bits(buf[margins]) == B.bits(B.store(layout, blk.sentinel).reshape(1))[0]).all()
         assert np.array_equal(B.bits(buf[~elem]), B.bits(F.filler(layout, int((~elem).sum()))))
         assert np.array_equal(B.bits(B.decode(layout, buf, F.N_ROWS, F.N_COLS, g.stride)), B.bits(blk.A))
+
+
+# ---- the far exemplars and candidates tests could fail -----------------------------------------------------------------------
+def differ(a, b):
+    return not np.array_equal(B.bits(np.asarray(a)), B.bits(np.asarray(b)))
+
+
+@pytest.mark.parametrize("kind", KINDS)
+@pytest.mark.parametrize("g", F.ALL, ids=lambda g: f"{g.layout}-{g.tag}")
+def test_a_narrowed_address_changes_what_the_far_tests_expect(g, kind):
+    """The references of tests/test_gpu_far_exemplars.py and tests/test_gpu_far_candidates.py on the rows, lists, covers
+    and k those tests use, on ``A`` and on ``A'``: an element whose offset changes when cut to int32 or to uint32 holds
+    the widened filler.  Wherever narrowing moves an element, the gains (for every cover, with and without a list), the
+    cover and the counters of every run, and the ids of every top-k differ."""
+    blk = F.block(g.layout, kind)
+    i = FC.counter(g, kind)
+    ex, ca = FC.exemplar_inputs(blk, i), FC.candidate_inputs(blk, i)
+    gains, covers = FC.exemplar_outputs(blk.A, ex)
+    topk = FC.candidate_outputs(blk.A, ca)
+    for bits in ("int32", "uint32"):
+        A2, moved = FC.narrowed(g, blk.A, bits)
+        if bits == "uint32" and g.layout == B.ROWMAJOR_F64:
+            assert moved == 0 and F.live_offsets(g).max() < P32           # it stays below 2^32 elements
+            continue
+        assert moved > 0
+        gains2, covers2 = FC.exemplar_outputs(A2, ex)
+        for key in gains:
+            assert differ(gains[key], gains2[key]), (bits, "gains", key)
+        for run, (c, r), (c2, r2) in zip(ex["cover_runs"], covers, covers2):
+            assert differ(c, c2) and differ(r, r2), (bits, "cover", run[0].tolist())
+        for run, (idx, _), (idx2, _) in zip(ca["runs"], topk, FC.candidate_outputs(A2, ca)):
+            assert differ(idx, idx2), (bits, "top-k ids", run[0], run[2] is None, run[4])
+
+
+@pytest.mark.parametrize("layout", B.LAYOUTS)
+def test_the_long_lists_tie_at_rank_k(layout):
+    """Every run of a not-staged list has, in every geometry, a row whose values at ranks k and k + 1 of the full order
+    are equal: the index passes of the selection decide."""
+    for g in F.geometries(layout):
+        for kind in KINDS:
+            blk = F.block(layout, kind)
+            inp = FC.candidate_inputs(blk, FC.counter(g, kind))
+            long = [run for run in inp["runs"] if run[0] == "long"]
+            assert len(long) == 2 * len(FC.LONG_KS) and all(run[1].size == FC.STAGED[layout] + 1 for run in long)
+            for run in long:
+                assert set(F.EDGE_COLS) <= set(run[1][F.N_COLS:].tolist())
+                assert FC.ties_at_k(blk.A, inp, run) >= 1, (g.tag, kind, run[2] is None, run[4])

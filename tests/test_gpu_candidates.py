@@ -4,8 +4,8 @@ nothing is summed that was not summed before.
 Kernel level, on synthetic blocks (tests/blocks.py, no fit): ``simrank_candidates_topk`` EQUALS ``candidates_ref.ref_topk``
 in all four layouts, on the blocks of tests/test_gpu_neighbors.py (a row of one repeated value, a row of both zeros, NaN
 and -inf), with the block's column ids a permutation (the id-sorted list has non-monotonic positions), on both sides of
-the staging cap, at the largest k and where one workgroup takes several turns; with every column listed it equals
-``simrank_neighbors_select``.
+the staging cap (the list that is not staged also at the largest k and with ids), at the largest k and where one
+workgroup takes several turns; with every column listed it equals ``simrank_neighbors_select``.
 
 Model level, at N = 300: ``most_similar``, ``score_sets`` and ``recommend`` with ``among=`` equal the NumPy statements on
 ``model.frame()`` and the unfiltered calls filtered, re-ranked and cut."""
@@ -110,7 +110,7 @@ def test_both_sides_of_the_staging_cap_and_the_largest_k(dev, layout):  # noqa: 
     c = _candidates.staged(layout)
     cases = [(2, 5100, [(5000, 4096)])]
     if c > 0:
-        cases.append((3, c + 70, [(m, k) for m in (c - 1, c, c + 1) for k in (1, 100)]))
+        cases.append((3, c + 70, [(m, k) for m in (c - 1, c, c + 1) for k in (1, 100)] + [(c + 1, _candidates.MAX_K)]))
     for n_rows, n_cols, runs in cases:
         tag, stride, base = B.variants(layout, n_rows, n_cols)[0]
         blk = B.make_long(layout, n_rows, n_cols, stride, 3)
@@ -121,6 +121,16 @@ def test_both_sides_of_the_staging_cap_and_the_largest_k(dev, layout):  # noqa: 
         for m, k in runs:
             pos = rng.permutation(n_cols)[:m]                           # (no ids: the list order alone decides the ties)
             check_topk(dev, where, blk.A, rows, row_pos, row_ids, pos, None, k, (layout, n_cols, m, k))
+        if c > 0 and n_cols > c:
+            # not staged, with ids: the columns' ids a permutation, the list sorted by id, every row's own id in it
+            col_ids = rng.permutation(n_cols).astype(np.int32)
+            cols = rng.permutation(n_cols)[:c + 1]
+            order = np.argsort(col_ids[cols], kind="stable")
+            pos, ids = cols[order], col_ids[cols][order]
+            own = ids[[7, c, 0, c // 2]]
+            assert (np.diff(ids) > 0).all() and (np.diff(pos) < 0).any()
+            check_topk(dev, where, blk.A, (rows[0], dev.put(own), row_pos.size), row_pos, own, pos, ids, 100,
+                       (layout, n_cols, c + 1, "ids"))
         dev.release()
 
 

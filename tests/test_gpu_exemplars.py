@@ -7,9 +7,11 @@ of 1024 (and four passes: the unrolled loop), with every row (NULL) and with sca
 rows outside on both sides, against covers of zeros, above every element, equal to elements (the strict ``>``) and mixed.
 On ``dyadic`` blocks every sum is exact, so a gain equals ``math.fsum`` of its terms bit for bit; on ``wide`` blocks it
 equals ``exemplars_ref.ordered_sum`` (the header's order restated) bit for bit and lies inside the stated bound.  Guard
-words after every output, a second run with the same bits, more listed rows than the grid cap.  ``cover`` with lists of
-1, 2 and 65 rows against ``exemplars_ref.block_cover``, the vector bit for bit and the counters exact from a start that
-is not zero.
+words after every output, a second run with the same bits, more listed rows than the grid cap.  Past one unrolled trip:
+ten widths from 3 075 to 12 289 columns at which a thread makes two and three unrolled trips, an unrolled trip and then
+single quads, and the threads of one wave part ways at the unrolled bound.  ``cover`` with lists of 1, 2 and 65 rows
+against ``exemplars_ref.block_cover``, the vector bit for bit and the counters exact from a start that is not zero, and
+on more columns than the grid's first turn holds.
 
 Model level: for every storage, a ``LocalWorld(3)``, compact, loaded and pruned models and both bipartite groups,
 ``lazy=True`` (with ``BATCH`` cut to 3) equals ``lazy=False`` in everything but ``evaluated``; ``coverage`` and
@@ -186,6 +188,77 @@ def test_more_listed_rows_than_the_grid_cap(dev, layout):
     assert np.isnan(want).sum() >= 3 and (want > 0).sum() > 2 * _exemplars.GRID_CAP
 
 
+CHUNK = 4 * _exemplars.THREADS                     # columns the workgroup covers in one pass
+UNROLL = 4                                         # passes of one unrolled trip
+LONG_COLS = (3075, 3076, 3077, 4100, 5001, 7171, 7172, 7173, 8193, 12289)
+LONG_DYADIC = (3076, 5001, 7173)
+
+
+def trips_of(n_cols):
+    """gains_kernel<L, true>'s three column loops restated: per thread its (unrolled trips, single-quad trips, element
+    trips) -> int [THREADS, 3]."""
+    out = np.zeros((_exemplars.THREADS, 3), dtype=np.int64)
+    for t in range(_exemplars.THREADS):
+        c0 = 4 * t
+        while c0 + (UNROLL - 1) * CHUNK + 4 <= n_cols:
+            c0, out[t, 0] = c0 + UNROLL * CHUNK, out[t, 0] + 1
+        while c0 + 4 <= n_cols:
+            c0, out[t, 1] = c0 + CHUNK, out[t, 1] + 1
+        while c0 < n_cols:
+            c0, out[t, 2] = c0 + CHUNK, out[t, 2] + 1
+    return out
+
+
+def check_the_long_widths_reach_every_regime():
+    trips ={n: trips_of(n) for n in LONG_COLS}
+    unrolled = {n: t[:, 0] for n, t in trips.items()}
+    assert not unrolled[3075].any() and unrolled[3076].tolist() == [1] + [0] * 255 == unrolled[3077].tolist()
+    assert (unrolled[7171] == 1).all() and unrolled[7172].tolist() == [2] + [1] * 255 == unrolled[7173].tolist()
+    split = [n for n in LONG_COLS if unrolled[n][:64].min() != unrolled[n][:64].max()]   # threads of one wave part ways
+    assert split == [3076, 3077, 7172, 7173]
+    assert [n for n in LONG_COLS if unrolled[n].max() >= 2] == [7172, 7173, 8193, 12289]
+    assert (unrolled[8193] == 2).all() and (unrolled[12289] == 3).all()
+    for n in (8193, 12289):                                                 # whole trips and one column: thread 0's
+        assert trips[n][:, 1].sum() == 0 and trips[n][:, 2].tolist() == [1] + [0] * 255
+    then_single = [n for n in LONG_COLS if ((trips[n][:, 0] >= 1) & (trips[n][:, 1] >= 1)).any()]
+    assert then_single == [4100, 5001, 7171, 7172, 7173]                    # (at 3076 thread 0 ends at 4096: nothing is left)
+    assert trips[4100][:, 1].tolist() == [1] + [0] * 255 and not trips[4100][:, 2].any()     # no partial quad
+    assert trips[5001][:, 1].sum() == 226 and trips[5001][226].tolist() == [1, 0, 1]         # and one
+    assert trips[3077][:, 2].sum() == 1 and trips[7173][:, 2].sum() == 1
+
+
+@pytest.mark.parametrize("layout", B.LAYOUTS)
+def test_gains_past_one_unrolled_trip(dev, layout):
+    """Widths at which a thread makes a second unrolled trip, an unrolled trip and then single quads, and at which the
+    threads of a wave part ways at the unrolled bound (``check_the_long_widths_reach_every_regime``); on the wide blocks
+    a running sum holds up to thirteen terms, so their order shows.  The crooked and offset variants take the element
+    path over 4 to 13 passes."""
+    check_the_long_widths_reach_every_regime()
+    n_rows = 3
+    rows = np.array([2, 0, 2, n_rows, 1, -1], dtype=np.int64)
+    for ci, (n_cols, kind) in enumerate([(n, "wide") for n in LONG_COLS] + [(n, "dyadic") for n in LONG_DYADIC]):
+        variants = B.variants(layout, n_rows, n_cols)
+        blk = block_of(layout, n_rows, n_cols, variants[0][1], 1300 + ci, kind) if kind == "wide" else \
+            B.make_long(layout, n_rows, n_cols, variants[0][1], 1300 + ci)
+        A = blk.A
+        rng = np.random.default_rng([ci, layout, 6])
+        covers = {name: c for name, c in covers_of(A, rng)[0].items() if name in ("zeros", "mixed")}
+        want = {name: (want_gains(A, None, c, kind), want_gains(A, rows, c, kind)) for name, c in covers.items()}
+        assert (want["mixed"][0] > 0).all()
+        for tag, stride, base in variants:
+            S = dev.put(B.encode(layout, A, stride, blk.sentinel).tobytes(), base)
+            for name, c in covers.items():
+                what = (layout, kind, n_cols, tag, name)
+                cover_dev = dev.put(np.append(c, GUARD_F64), 8 if tag == "offset" else 0)
+                got = run_gains(dev, S, layout, stride, n_rows, n_cols, None, cover_dev)
+                same_bits(got, np.append(want[name][0], GUARD_F64), what + ("every row",))
+                got_l = run_gains(dev, S, layout, stride, n_rows, n_cols, rows, cover_dev)
+                same_bits(got_l, np.append(want[name][1], GUARD_F64), what + ("listed",))
+                again = run_gains(dev, S, layout, stride, n_rows, n_cols, rows, cover_dev)
+                assert np.array_equal(B.bits(got_l), B.bits(again)), what
+            dev.release()
+
+
 # ---- 2. cover on synthetic blocks -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("layout", B.LAYOUTS)
 def test_cover_equals_the_reference(dev, layout):
@@ -214,6 +287,34 @@ def test_cover_equals_the_reference(dev, layout):
                     assert got_r.tolist() == want_r.tolist() + [GUARD_U32], what
                 dev.release()
     assert raised_some >= 100
+
+
+@pytest.mark.parametrize("layout", B.LAYOUTS)
+def test_cover_second_turn_of_the_column_loop(dev, layout):
+    """More columns than GRID_CAP workgroups of THREADS hold: the first 257 threads of the grid take a second turn."""
+    first_turn = _exemplars.GRID_CAP * _exemplars.THREADS
+    n_rows, n_cols = 2, first_turn + 257
+    tag, stride, base = B.variants(layout, n_rows, n_cols)[0]
+    blk = B.make_long(layout, n_rows, n_cols, stride, 41)
+    A = blk.A
+    rng = np.random.default_rng([layout, 41])
+    start = covers_of(A, rng)[0]["mixed"]
+    S = dev.put(blk.raw, base)
+    for rows in ([1], [1, 0, 2, 1]):                                        # (row 2 is outside)
+        first = rng.integers(1, 1000, size=len(rows))
+        want_c, want_r = ER.block_cover(A, rows, start, first)
+        got_c, got_r = run_cover(dev, S, layout, stride, n_rows, n_cols, rows, start, first)
+        same_bits(got_c, np.append(want_c, GUARD_F64), (layout, rows, "cover"))
+        assert got_r.tolist() == want_r.tolist() + [GUARD_U32], (layout, rows)
+        # the expected counters rise in columns of the first turn and of the second
+        cover = start.copy()
+        for i, r in enumerate(rows):
+            if r < n_rows:
+                up = A[r] > cover
+                assert up.sum() == want_r[i] - first[i]
+                assert i > 1 or (up[:first_turn].any() and up[first_turn:].any()), (layout, rows, i)
+                cover[up] = A[r][up]
+        assert len(rows) == 1 or (want_r[2] == first[2] and want_r[3] == first[3])      # a row outside, a row again
 
 
 # ---- 3. through the estimators ----------------------------------------------------------------------------------------------------

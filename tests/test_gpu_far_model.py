@@ -1,7 +1,7 @@
 """The wrappers of the companion libraries at real N: BASELINE config 5 (SimRank++ on ``pl65536``, N = 65536), kept and
 compact, so that a row of the model starts up to 2^32 floats into one 17.2 GB matrix and the ctypes prototypes, column
-maps and band loops of ``_sets.py``, ``_rank.py``, ``_neighbors.py``, ``_profile.py`` and ``_cluster.py`` run where the
-README presents them.  Nothing needs the N x N frame on the host: every reference is evaluated on ``model.rows(...)`` of
+maps and band loops of ``_sets.py``, ``_rank.py``, ``_neighbors.py``, ``_profile.py``, ``_cluster.py``,
+``_candidates.py`` and ``_exemplars.py`` run where the README presents them.  Nothing needs the N x N frame on the host: every reference is evaluated on ``model.rows(...)`` of
 the rows a query reads (``rows`` at this N is tied to a float64 recomputation by tests/test_gpu_query.py and
 tests/test_gpu_fullsize.py), for 64 nodes spread over [0, N), node N - 1 included, and every comparison but one is exact.
 
@@ -19,10 +19,12 @@ import pytest
 from pandas.testing import assert_frame_equal
 
 import simrank_amd.SimRank as SRA
-from simrank_amd import synth
+from simrank_amd import _candidates, _exemplars, synth
 from simrank_amd.engine import HipOps
 from tests import blocks as B
+from tests import candidates_ref as CA
 from tests import cluster_ref as CR
+from tests import exemplars_ref as ER
 from tests import foldin_ref as FR
 from tests import rank_ref as K
 from tests import sets_ref as SR
@@ -202,6 +204,111 @@ def test_threshold_count_pairs_and_components_agree(model):
     want = CR.labels_of_edges(N, zip(a.tolist(), b.tolist()))
     assert np.array_equal(comp.to_numpy(), want)
     assert 1 < want.max() + 1 < N                                            # neither one cluster nor none
+
+
+def long_of(node_labels, lab, idx, val, k):
+    """The long frame (node, rank, neighbor, similarity) of a reference's (positions, values) [n_q, k]."""
+    keep = idx.ravel() >= 0
+    return pd.DataFrame({"node": np.repeat(np.asarray(node_labels), k)[keep], "rank": np.tile(np.arange(1, k + 1), len(idx))[keep],
+                         "neighbor": lab.take(idx.ravel()[keep]), "similarity": val.ravel()[keep]})
+
+
+def spread(m):
+    """m distinct positions spread over [0, N), the first and the last node among them."""
+    S = np.linspace(0, N - 1, m).astype(np.int64)
+    assert np.unique(S).size == m and S[0] == 0 and S[-1] == N - 1
+    return S
+
+
+def test_most_similar_among_and_exclude(model):
+    """Candidate sets on both sides of the staging cap (a quarter of the nodes) and ``exclude=`` of five labels alone:
+    N - 5 candidates, not staged, 16 index bits.  The reference reads the 64 rows and nothing else."""
+    est, labels = model
+    lab, P = pd.Index(labels), sample()
+    nodes = lab.take(P)
+    R = est.rows(nodes).values
+    (block,) = est._model[0]._reader(0).blocks
+    cap = _candidates.staged(block["layout"])
+    assert cap == N // 4
+    at_cap = spread(cap)
+    one_more = np.union1d(at_cap, [int(np.setdiff1d(np.arange(N // 2, N // 2 + 8), at_cap)[0])])
+    gone = np.array([0, 3, N // 2, N - 2, N - 1], dtype=np.int64)
+    rest = np.setdiff1d(np.arange(N), gone)
+    assert one_more.size == cap + 1 and rest.size == N - 5 > 1 << 15
+    far = 0
+    for cand, kw in ((at_cap, {"among": lab.take(at_cap)}), (one_more, {"among": lab.take(one_more)}),
+                     (rest, {"exclude": lab.take(gone)})):
+        for k in (10, _candidates.MAX_K):
+            got = est.most_similar(list(nodes), k, **kw)
+            idx, val = CA.ref_topk(R, np.arange(P.size), P, cand, cand, k)
+            want = long_of(nodes, lab, idx, val, k)
+            assert_frame_equal(got.reset_index(drop=True), want, check_exact=True, check_dtype=False)
+            assert (idx >= 0).all() and (val[:, 0] > 0).any()
+            far += int(((idx >= 1 << 15) & (val > 0)).sum())
+    assert far > 0                                                       # neighbours past 2^15: columns of the far panels
+
+
+def test_score_sets_among(model):
+    """The baskets of ``test_score_sets_and_rank_sets`` among one label more than the staging cap and half the sampled
+    nodes: the dense scores of that test with the columns outside the set removed."""
+    est, labels = model
+    P, rng = sample(), np.random.default_rng(1)
+    lab = pd.Index(labels)
+    R = est.rows(lab.take(P)).values
+    at = {int(p): i for i, p in enumerate(P)}
+    sets, weights = baskets(P, rng)
+    names = [f"s{q}" for q in range(len(sets))]
+    sets_lab = [list(lab.take(np.asarray(s, dtype=np.int64))) for s in sets]
+    dense = SR.scores(R, [[at[int(p)] for p in s] for s in sets], [np.asarray(w) for w in weights])
+    cand = np.union1d(spread(N // 4 + 1), P[::2])
+    got = est.score_sets(sets_lab, weights=weights, names=names, top_k=10, among=list(lab.take(cand)))
+    inside = [np.searchsorted(cand, [p for p in s if p in set(cand.tolist())]).tolist() for s in sets]
+    want = SR.long_frame("set", pd.Index(names), lab.take(cand), dense[:, cand], 10, inside)
+    assert_frame_equal(got.reset_index(drop=True), want.reset_index(drop=True), check_exact=True)
+    assert sum(len(x) for x in inside) >= 32 and (want["score"] != 0).any()
+
+
+@pytest.mark.parametrize("with_given", [False, True], ids=["no given", "given the last node"])
+def test_exemplars(model, monkeypatch, with_given):
+    """Six picks at N = 65536: a ``gains`` row is 16 trips of the unrolled loop, ``cover`` is 512 KiB, and the given row,
+    which ``cover`` reads first, starts past 2^32 floats.  Lazy (in rounds of 64) equals plain; coverage, raised counts
+    and gains against the NumPy statement on ``rows`` of the given and picked nodes; greedy as far as the 64 sampled
+    rows can tell."""
+    est, labels = model
+    lab, P, k = pd.Index(labels), sample(), 6
+    given = [labels[N - 1]] if with_given else None
+    at = [N - 1] if with_given else []
+    monkeypatch.setattr(_exemplars, "BATCH", 64)
+    picks, coverage = est.exemplars(k, given=given, lazy=True)
+    monkeypatch.undo()
+    plain, coverage_p = est.exemplars(k, given=given, lazy=False)
+    assert picks["exemplar"].tolist() == plain["exemplar"].tolist()
+    same_bits(picks["gain"].to_numpy(), plain["gain"].to_numpy(), "lazy gain")
+    assert picks["raised"].tolist() == plain["raised"].tolist()
+    same_bits(coverage.to_numpy(), coverage_p.to_numpy(), "lazy coverage")
+    assert plain["evaluated"].tolist() == [N - len(at) - p for p in range(k)]
+    assert picks["evaluated"].sum() < plain["evaluated"].sum()
+    picked = lab.get_indexer(picks["exemplar"]).tolist()
+    assert len(set(picked)) == k and not set(picked) & set(at) and coverage.index.equals(lab)
+    Rk = est.rows(lab.take(np.asarray(at + picked, dtype=np.int64))).values
+    R = est.rows(lab.take(P)).values
+    same_bits(coverage.to_numpy(), ER.coverage(Rk), "coverage")
+    gain = picks["gain"].to_numpy()
+    cover = np.zeros(N)
+    for row in Rk[:len(at)]:
+        ER.apply(row, cover)
+    others = [i for i, p in enumerate(P) if int(p) not in set(at + picked)]
+    for p, row in enumerate(Rk[len(at):]):
+        t = ER.terms(row, cover)
+        assert abs(gain[p] - ER.exact_sum(t)) <= ER.bound(t), (p, gain[p], ER.exact_sum(t), ER.bound(t))
+        # the compact model is the canonical form: the sum runs in the frame's order
+        assert gain[p] == ER.ordered_sum(t), (p, gain[p], ER.ordered_sum(t))
+        for i in others:
+            g = ER.ordered_sum(ER.terms(R[i], cover))
+            assert g < gain[p] or (g == gain[p] and P[i] > picked[p]), (p, int(P[i]), g, gain[p])
+        assert picks["raised"][p] == ER.apply(row, cover), p
+    same_bits(cover, coverage.to_numpy(), "cover")
+    assert gain[0] > 0 and (np.diff(gain) <= 0).all() and len(others) >= 64 - k - 1
 
 
 def test_prune_keeps_the_ten_best_of_every_sampled_row():
